@@ -19,7 +19,12 @@ digest xors all-gathered, over RCCL (torch.distributed on the nccl group); every
 the whole-problem result and verifies it.  ``value`` = itemsets of the problem ÷ the slowest
 rank's step.
 
-Secondary fields:
+A plain run (``bench.py --gpus 1 --steps N --warmup W``) sets up, warms up, times the N headline
+steps and prints the result line; ``--dump-outputs DIR`` also writes what the last timed step
+returned (per-size counts, totals, digest) as ``DIR/<name>.npy``.  Everything below is measured
+only with ``--full``.
+
+Secondary fields (``--full``):
 * ``serve.hip_loop`` — the same harness with the persistent HIP serving kernel forced
                     (``SERVE_BACKEND=loop``): every request answered by the polling kernel.
 * ``serve``       — config 4, run FIRST in a fresh child process (this process has not touched
@@ -147,6 +152,25 @@ def run_serve_child(qps: str, duration: float, backend: str, timeout: float = 42
     return out
 
 
+def dump_outputs(path: str, r: dict) -> None:
+    """What the last timed headline step returned to its caller (the whole-problem result of
+    ``DeepMiner.mine``), one float64 ``.npy`` per field; every value is an integer below 2^53,
+    so float64 holds it exactly.  The 128-bit digest is written as four 32-bit words (sum high,
+    sum low, xor high, xor low)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    dg = r["digest"]
+    arrays = {
+        "per_level": [int(x) for x in r["per_level"]],
+        "n_itemsets": [int(r["n_itemsets"])],
+        "max_depth": [int(r["max_depth"])],
+        "n_frequent_items": [int(r["n_frequent_items"])],
+        "digest_words": [int(dg[i:i + 8], 16) for i in range(0, 32, 8)],
+    }
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v, dtype=np.float64))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -176,7 +200,16 @@ def main() -> int:
                     help="CPU tier of the headline (native CPU count miner, gloo): no GPU")
     ap.add_argument("--comm", default=os.environ.get("KMLS_BENCH_COMM", "torch"),
                     help="N>1 headline combine: torch (torch.distributed/RCCL) | rccl | host")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary section (serve, emit, job_full, levelwise, "
+                         "config 2/3/5, native_rccl); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed headline step returned as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the headline steps, print the line
+        args.serve_qps = ""
+        args.no_emit = args.no_job = args.no_levelwise = True
+        args.no_config2 = args.no_config3 = args.no_config5 = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -274,6 +307,9 @@ def main() -> int:
                     cpu=args.cpu)
     wd.disarm()
     deep_miner = h.pop("_miner")
+    last = h.pop("_last")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     if args.seed != 0:
         h["verified_digest"] = None
     ms_step = h["ms_per_step"]
@@ -379,7 +415,8 @@ def main() -> int:
         wd.disarm()
 
     # ---- the headline combine through the native RCCL communicator ----
-    if world > 1 and dist_backend == "nccl" and args.comm != "rccl" and not args.cpu:
+    if args.full and world > 1 and dist_backend == "nccl" and args.comm != "rccl" \
+            and not args.cpu:
         os.environ.setdefault("KMLS_COMM_TIMEOUT_S", "60")
         wd.arm("native_rccl", 240)
         try:

@@ -12,6 +12,8 @@
 #include <string>
 #include <vector>
 
+#include <unistd.h>
+
 #include "kmls/host.hpp"
 
 using namespace kmls;
@@ -107,7 +109,13 @@ int main() {
   CHECK(n1 >= -1 && n1 <= 10);
   for (int i = 1; i < n1; ++i) CHECK(sc[i - 1] >= sc[i]);
   // 4. CSV ingest + group-by (quotes, embedded commas, escaped quotes)
-  const char* path = "/tmp/kmls_selftest.csv";
+  // a file of this run's own in the temporary directory (no fixed name shared between users)
+  const char* tmpdir = std::getenv("TMPDIR");
+  std::string path_s = std::string(tmpdir && *tmpdir ? tmpdir : "/tmp") + "/kmls_selftest_XXXXXX";
+  const int path_fd = mkstemp(&path_s[0]);
+  CHECK(path_fd >= 0);
+  close(path_fd);
+  const char* path = path_s.c_str();
   {
     std::ofstream f(path);
     f << "pid,track_name,artist_name\n";

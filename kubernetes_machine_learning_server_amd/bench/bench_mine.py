@@ -120,6 +120,7 @@ def run_deep(tx, ms: float, world: int, rank: int, device: int, warmup: int, ste
     out["verified_digest"] = (r["digest"] == ref[0] and int(r["n_itemsets"]) == ref[1]) \
         if ref else None
     out["_miner"] = dm
+    out["_last"] = r
     return out
 
 

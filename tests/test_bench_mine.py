@@ -56,3 +56,49 @@ def test_config5_pvc_alt_index_is_the_higher_support_rule_map(tmp_path):
         assert list(zip(got_c, got_n)) == want
     assert (tmp_path / "api-data" / "pickles" / "best_tracks.pickle").exists()
     assert (tmp_path / "api-data" / "last_execution.txt").read_text() == "initial"
+
+
+def test_bench_dump_outputs_cpu_tier(tmp_path):
+    """``bench.py --dump-outputs`` on the CPU tier: a plain run prints one result line without
+    the ``--full`` sections, and the dumped arrays are the last timed step's result: float64,
+    equal to the CPU count miner's per-size counts, total and digest, identical from run to
+    run."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    from kubernetes_machine_learning_server_amd.data.synthetic import generate
+    from kubernetes_machine_learning_server_amd.ops import native
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=root)
+    dumps = []
+    for name in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--cpu", "--steps",
+               "2", "--warmup", "1", "--min-support", "0.05", "--dump-outputs",
+               str(tmp_path / name)]
+        p = subprocess.run(cmd, env=env, cwd=str(tmp_path), capture_output=True, text=True,
+                           timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert k in out
+        for k in ("serve", "emit", "job_full", "levelwise_0.05", "config2", "config3", "config5"):
+            assert k not in out
+        d = {f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))}
+        assert all(a.dtype == np.float64 for a in d.values())
+        dumps.append(d)
+    a, b = dumps
+    assert sorted(a) == sorted(b) == ["digest_words", "max_depth", "n_frequent_items",
+                                      "n_itemsets", "per_level"]
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    tx = generate("ds1", seed=0)
+    ref = native.load().mine_cpu_count(tx.tx_ptr, tx.items, tx.n_items, 0.05)
+    assert a["per_level"].astype(np.int64).tolist() == [int(x) for x in ref["per_level"]]
+    assert int(a["n_itemsets"][0]) == int(ref["n_itemsets"]) == 77905
+    words = "".join(f"{int(w):08x}" for w in a["digest_words"])
+    assert words == ref["digest"] == out["digest"]
