@@ -490,6 +490,9 @@ void register_gpu_bindings(py::module_& m) {
         d["round_tasks"] = r.round_tasks;
         d["spilled_tasks"] = r.spilled_tasks;
         d["handoffs"] = r.handoffs;
+        d["leaf_candidates"] = r.leaf_candidates;
+        d["leaf_m_default"] = gpu::kDeepLeafDefault;
+        d["leaf_m_max"] = kern::deep_leaf_max();
         d["round_ms"] = r.round_ms;
         py::dict ph;
         ph["prologue"] = r.ms_prologue;

@@ -114,6 +114,7 @@ DeepResult GpuMiner::mine_deep(double min_support, int max_len, int rank, int wo
   res.round_tasks = loc.round_tasks;
   res.spilled_tasks = loc.spilled_tasks;
   res.handoffs = loc.handoffs;
+  res.leaf_candidates = (int64_t)loc.leaf_candidates;
   res.round_ms = loc.round_ms;
   res.ms_root = loc.ms_root;
   res.ms_rounds = loc.ms_rounds;

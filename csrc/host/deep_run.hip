@@ -381,6 +381,10 @@ DeepLocal deep_run(DeepBufs& b, const DeepInput& in, int rank, int world, const 
   a.minsup = in.minsup;
   a.max_len = in.max_len;
   a.split_min = opt.split_min;
+  // count-only: classes of up to kDeepLeafDefault members are finished in one leaf step
+  // (profiles/leaf_step_headline.md; 0 = the row / batch steps only); emit mode never takes it
+  a.leaf_m = (unsigned)std::max<long long>(
+      0, std::min<long long>(kern::deep_leaf_max(), test_hook("deep_leaf_m", kDeepLeafDefault)));
   // hand-offs split classes of >= 32 first members, keeping 5/16 of them (1 GPU: 29.3-29.9 ms
   // against 30.0-31.1 unsplit; 8 ranks: 8.1-8.3 vs 7.9-8.2 unsplit, 8.5-9.1 at >= 8 members)
   a.split_firsts = (unsigned)std::max<long long>(2, test_hook("deep_split_firsts", 32));
@@ -582,6 +586,7 @@ DeepLocal deep_run(DeepBufs& b, const DeepInput& in, int rank, int world, const 
   res.dsum = b.h_ctl->digest_sum;  // level-2 terms (rank 0) + the rounds
   res.dxor = b.h_ctl->digest_xor;
   res.candidates = b.h_ctl->candidates;
+  res.leaf_candidates = b.h_ctl->leaf_candidates;
   res.chunks = b.h_ctl->chunks;
   return res;
 }

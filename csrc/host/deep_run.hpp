@@ -106,6 +106,7 @@ struct DeepInput {
 struct DeepLocal {
   std::vector<uint64_t> per_depth = std::vector<uint64_t>(64, 0);
   uint64_t dsum = 0, dxor = 0, candidates = 0, chunks = 0;
+  uint64_t leaf_candidates = 0;  // of candidates: subsets evaluated by leaf steps
   int64_t level2_tasks = 0;
   int maxt = 0;  // widest block tier of the count kernel instance
   std::vector<int64_t> round_tasks;

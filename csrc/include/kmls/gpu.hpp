@@ -186,6 +186,9 @@ struct DeepOpts {
   // item rank, support, size), kept on the device after the call (GpuMiner::deep_arena_*)
   bool emit = false;
 };
+// count-only: plain classes of up to this many members are finished in one leaf step (deep.hip;
+// the test hook deep_leaf_m overrides it, 0 = no leaf steps)
+constexpr int kDeepLeafDefault = 7;
 struct DeepResult {
   std::vector<uint64_t> per_level;  // [d] = frequent itemsets of size d (index 0 unused)
   int64_t n_itemsets = 0, n_frequent_items = 0, candidates = 0, chunks = 0, level2_tasks = 0;
@@ -194,6 +197,10 @@ struct DeepResult {
   std::vector<int64_t> round_tasks;
   int64_t spilled_tasks = 0;
   int64_t handoffs = 0;
+  // `candidates` counts AND+popcount evaluations: a leaf step (count-only, deep.hip) evaluates
+  // every subset of a small class, so the total may exceed the depth-first walk's.  Of them,
+  // leaf_candidates were evaluated in leaf steps (this rank's; 0 = the path did not run).
+  int64_t leaf_candidates = 0;
   std::vector<double> round_ms;
   double ms_prologue = 0, ms_root = 0, ms_rounds = 0, ms_combine = 0, ms_total = 0;
   double ms_assign = 0;               // task costs + ordering (inside ms_root)

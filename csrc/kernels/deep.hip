@@ -26,6 +26,11 @@
 //   member PAIRS fill up to kCap lanes, so a wave64 instruction still carries 64 candidates when
 //   classes have 5-20 members.  Survivors of one (frame, member) group stay contiguous in the
 //   child block (lane order = pair order), so each group becomes a child frame.
+// * Leaf step (count-only; plain classes of at most DeepArgs::leaf_m <= kLeafMax members in a
+//   block of a tier <= kLeafTier): the whole subtree of each of the top sibling frames in one
+//   step, one lane per member subset, the member rows staged in LDS; nothing is written and no
+//   child frame is pushed (leaf_step).  Most of the tree's candidates sit in such classes, so
+//   most child rows are never stored to the HBM stacks or read back.
 // * Load balance: tasks are dequeued by ticket, heaviest first (deep_order.hip's cost order).
 //   Steal mode (the default): a wave whose ticket finds the queue drained opens its inbox and
 //   asks busy waves, one mailbox at a time; a busy wave past its step budget that finds a request
@@ -60,6 +65,37 @@ constexpr unsigned kMaxLead = 2047;    // frame lead field (11 bits)
 // (hand-offs split a class of >= DeepArgs::split_firsts first members, keeping split_keep16/16)
 constexpr unsigned kDone = 1u << 31;   // steal mode: ready-flag value epoch ^ kDone = no task
 constexpr unsigned kNodeChunk = 4096;  // emit mode: node ids a wave takes from ctl->node_top
+// leaf step (count-only): classes of at most DeepArgs::leaf_m <= kLeafMax members
+constexpr int kLeafMax = 8;
+constexpr int kLeafSlots = kCap;     // subset lanes one leaf step may take (as a batch: kCap pairs)
+constexpr int kLeafStage = 512;      // words of LDS the taken frames' rows are staged in
+constexpr int kLeafTier = 16;        // widest block tier the leaf step is instantiated for
+constexpr int kLeafUnroll = 8;       // members of a subset whose staged rows are read at once
+static_assert(kLeafStage * 8 == kCap * 2 * 4, "the staged rows share the batch step's group tables");
+static_assert(kLeafSlots <= kCap && kLeafSlots >= (1 << kLeafMax) - kLeafMax - 1,
+              "frame-start flags fit g_flag; the top frame alone always fits");
+static_assert(kLeafStage / (kLeafTier + 1) >= 2 * kLeafMax, "the top frame alone always fits the stage");
+
+// The j-th (from 0) of the member subsets with at least two members, as a bit mask, in increasing
+// mask order: 3, 5, 6, 7, 9, ...  The subsets of a class of m members are the first 2^m - m - 1
+// of them, for every m.  (Below x there are x - 2 - bitlen(x) masks with two bits or more when x
+// has two itself: all but 0 and the powers of two; so x = j + bitlen(x) + 1, and bitlen(j + 2) is
+// bitlen(x) or one less.)
+__host__ __device__ constexpr unsigned leaf_subset(unsigned j) {
+  const unsigned b = 32u - (unsigned)__builtin_clz(j + 2u);
+  const unsigned x = j + b + 1u;
+  return x + ((x >> b) ? 1u : 0u);
+}
+constexpr bool leaf_subset_ok() {
+  unsigned j = 0;
+  for (unsigned x = 0; x < (1u << kLeafMax); ++x)
+    if ((x & (x - 1u)) != 0u && x != 0u) {
+      if (leaf_subset(j) != x) return false;
+      ++j;
+    }
+  return j == (1u << kLeafMax) - kLeafMax - 1u;
+}
+static_assert(leaf_subset_ok(), "leaf_subset enumerates the masks of >= 2 bits in order");
 
 // frame meta: bits 0..5 prefix size, bit 6 single, bits 7..13 block width (words), bits 14..20
 // block-stack index + 1 (0 = external), bits 21..31 lead: how many of the class's members, from
@@ -263,13 +299,21 @@ struct WaveLds {
   // member-group tables in 16 bits (every value < kCap; frames of a batch have <= 32 members):
   // with the u32 block bases, 8 KB of LDS per wave instead of 12.5, so four 4-wave workgroups
   // fit a CU's 160 KB
-  unsigned short g_cnt[kCap], g_start[kCap];
-  unsigned short g_pos[kCap];       // first pair of member group g (its run start)
-  unsigned short g_fi[kCap];        // frame << 8 | member of group g
-  unsigned long long g_flag[kCap / 64];  // bit p: a group starts at pair p
+  union {
+    struct {
+      unsigned short g_cnt[kCap], g_start[kCap];
+      unsigned short g_pos[kCap];   // first pair of member group g (its run start)
+      unsigned short g_fi[kCap];    // frame << 8 | member of group g
+    };
+    // leaf step (the group tables are idle then): the taken frames' slot range of the block,
+    // [word row][slot] at a per-tier row stride, the item-hash row last
+    unsigned long long leaf_rows[kLeafStage];
+  };
+  unsigned long long g_flag[kCap / 64];  // bit p: a group (leaf step: a frame) starts at pair p
   unsigned b_base[kBStack];         // byte offset in the wave's stack region (< 4 GB)
   unsigned b_live[kBStack];
   unsigned long long depth_cnt[64];
+  unsigned long long leaf_cands;    // subsets evaluated by leaf steps (of WaveAcc::cands)
   ProjLds<MAXT> proj;
 };
 
@@ -843,15 +887,154 @@ __device__ __forceinline__ void batch_step(const DeepArgs& a, DeepFrame* fst, Wa
   }
 }
 
+// ---- leaf step (count-only): the whole subtrees of the top frames' small classes, at once ----
+// Support is anti-monotone and all rows of a block share one tid projection, so for a class of
+// members x_0..x_{m-1} under prefix P the itemset P ∪ S (S a subset of the members, |S| >= 2) is
+// frequent iff popcount(AND of the rows of S) >= minsup, whatever a depth-first walk would have
+// pruned on its way there.  The step takes the run of frames from the top of the stack that are
+// in lane registers, share the top frame's block (one base, pad, width and depth) and are plain
+// classes of 2..leaf_m members; every subset of every such class gets a lane (lane order: frame
+// by frame, the subsets of a frame in leaf_subset order), 64 per pass.  Nothing is written: no
+// child block, no child frames, no further steps for those subtrees.  Some subsets are evaluated
+// that the walk would have pruned (< 5 % more at ds1 @0.02 with leaf_m 6).
+// The frames' member rows are staged in LDS once per step: frames of one block lie next to each
+// other in slot order (their singleton neighbours between them), so the step stages the slot
+// range the run spans and ends the run where that range outgrows the stage.
+template <int WT, int MAXT>
+__device__ __forceinline__ void leaf_step(const DeepArgs& a, WaveState& st, WaveLds<MAXT>& L,
+                                          const DeepFrame& top, const DeepFrame& lf, int lane,
+                                          WaveAcc& acc) {
+  static_assert(WT <= kLeafTier, "leaf step tiers");
+  constexpr unsigned kStride = (unsigned)kLeafStage / (unsigned)(WT + 1);  // slots per staged row
+  const unsigned depth = meta_depth(top.meta);
+  // frame f (from the top) = lane f's registers, as in batch_step
+  const unsigned fm = lf.m;
+  const bool elig = (unsigned)lane < st.nf && lf.blk == top.blk &&
+                    ((lf.meta ^ top.meta) & 0x3fffu) == 0u &&  // depth, plain, width
+                    meta_lead(lf.meta) == 0u && fm >= 2u && fm <= a.leaf_m;
+  const unsigned fc = elig ? (1u << fm) - fm - 1u : 0u;  // its subsets
+  unsigned incl = fc, lo = lf.s0, hi = lf.s0 + fm;
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned oi = __shfl_up(incl, off, 64), ol = __shfl_up(lo, off, 64),
+                   oh = __shfl_up(hi, off, 64);
+    if (lane >= off) {
+      incl += oi;
+      lo = ol < lo ? ol : lo;
+      hi = oh > hi ? oh : hi;
+    }
+  }
+  // (prefix property: an ineligible frame makes every later lane fail through the ballot below;
+  // the sums cannot wrap: 64 frames of < 2^kLeafMax subsets)
+  const unsigned long long eligm = __ballot(elig);
+  const unsigned run = eligm == ~0ull ? 64u : (unsigned)__builtin_ctzll(~eligm);
+  const unsigned long long okm = __ballot((unsigned)lane < run && incl <= (unsigned)kLeafSlots &&
+                                          hi - lo + (unsigned)kLeafMax <= kStride);
+  unsigned k = okm == ~0ull ? 64u : (unsigned)__builtin_ctzll(~okm);
+  if (k == 0) k = 1;  // (the dispatch found the top frame eligible; alone it always fits)
+  k = uni(k);
+  const unsigned total = uni(__shfl(incl, (int)k - 1, 64));
+  const unsigned smin = uni(__shfl(lo, (int)k - 1, 64));
+  const unsigned range = uni(__shfl(hi, (int)k - 1, 64)) - smin;
+  unsigned mmax = 2;  // the largest class taken: bounds the member loop
+#pragma unroll
+  for (unsigned i = 3; i <= (unsigned)kLeafMax; ++i)
+    if (__ballot((unsigned)lane < k && fm >= i)) mmax = i;
+  if (lane < (int)(kCap / 64)) L.g_flag[lane] = 0ull;
+  __builtin_amdgcn_wave_barrier();
+  if ((unsigned)lane < k) {
+    const unsigned base = incl - fc;
+    L.f_hash[lane] = lf.hash;
+    L.f_s0[lane] = lf.s0 - smin;
+    L.f_meta[lane] = lf.meta;
+    L.P[lane] = base;
+    atomicOr(&L.g_flag[base >> 6], 1ull << (base & 63));  // (every frame has >= 1 subset)
+  }
+  {
+    const gptr<const unsigned long long> blk = as_global_addr<const unsigned long long>(top.blk);
+#pragma unroll
+    for (int w = 0; w <= WT; ++w) {
+      const gptr<const unsigned long long> row = blk + (unsigned long long)w * top.pad + smin;
+      for (unsigned j = lane; j < range; j += 64) L.leaf_rows[(unsigned)w * kStride + j] = row[j];
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  unsigned fbase = 0, dc = 0;  // dc: lane kk's count of frequent subsets of kk members
+  unsigned long long evaluated = 0;
+  for (unsigned c0 = 0; c0 < total; c0 += 64) {
+    const unsigned p = c0 + lane;
+    const unsigned long long gw = uni64(L.g_flag[(c0 >> 6) + vzero()]);
+    // the lane's frame: frame starts at or before its slot (lanes past the end: the last frame)
+    const unsigned f = fbase + (unsigned)__popcll(gw & ((2ull << lane) - 1ull)) - 1u;
+    fbase += (unsigned)__popcll(gw);
+    const unsigned mask = p < total ? leaf_subset(p - L.P[f]) : 3u;
+    const unsigned kk = (unsigned)__popc(mask);
+    const bool act = p < total && (a.max_len == 0 || (int)(depth + kk) <= a.max_len);
+    const unsigned o = L.f_s0[f];
+    unsigned long long h = L.f_hash[f];
+    unsigned long long v[WT];
+#pragma unroll
+    for (int w = 0; w < WT; ++w) v[w] = ~0ull;
+#pragma unroll kLeafUnroll
+    for (unsigned i = 0; i < (unsigned)kLeafMax; ++i) {
+      if (i >= mmax) break;  // (uniform)
+      if ((mask >> i) & 1u) {
+#pragma unroll
+        for (int w = 0; w < WT; ++w) v[w] &= L.leaf_rows[(unsigned)w * kStride + o + i];
+        h += L.leaf_rows[(unsigned)WT * kStride + o + i];
+      }
+    }
+    unsigned c = 0;
+#pragma unroll
+    for (int w = 0; w < WT; ++w) c += (unsigned)__popcll(v[w]);
+    const bool surv = act && c >= a.minsup;
+    if (surv) {
+      const DigestTerms dt = digest_terms(h, c);
+      acc.dsum += dt.sum;
+      acc.dxor ^= dt.xr;
+    }
+    // lanes of one pass differ in size: one ballot per size, counted by lane kk
+#pragma unroll
+    for (unsigned q = 2; q <= (unsigned)kLeafMax; ++q) {
+      if (q > mmax) break;  // (uniform)
+      const unsigned n = (unsigned)__popcll(__ballot(surv && kk == q));
+      if ((unsigned)lane == q) dc += n;
+    }
+    evaluated += (unsigned long long)__popcll(__ballot(act));
+    ++acc.chunks;
+  }
+  if ((unsigned)lane >= 2u && (unsigned)lane <= mmax && dc && depth + (unsigned)lane < 64u)
+    L.depth_cnt[depth + (unsigned)lane] += dc;
+  acc.cands += evaluated;
+  if (lane == 0) L.leaf_cands += evaluated;
+  acc.budget_used += (total + 63) / 64;
+  // the k taken frames leave the stack (as in batch_step); nothing is pushed
+  if ((unsigned)lane < k) {
+    const unsigned b = meta_bidx(L.f_meta[lane]);
+    if (b) atomicSub(&L.b_live[b - 1], 1u);
+  }
+  st.nf -= k;
+  __builtin_amdgcn_wave_barrier();
+}
+
+// the kinds of step
+enum StepKind { kStepBatch = 0, kStepRow = 1, kStepLeaf = 2 };
+
 // one step of the top frame, dispatched on its block width (wave-uniform)
 template <int MAXT, bool EMIT, int T0, int... Ts>
-__device__ __forceinline__ void step_tier(unsigned wt, bool row_mode, const DeepArgs& a,
+__device__ __forceinline__ void step_tier(unsigned wt, StepKind kind, const DeepArgs& a,
                                           DeepFrame* fst, WaveState& st, WaveLds<MAXT>& L,
                                           const DeepFrame& top, const DeepFrame& lf,
                                           const WaveStack& stack, int lane, WaveAcc& acc) {
   if constexpr (T0 <= MAXT) {
     if (wt == (unsigned)T0) {
-      if (row_mode)
+      if constexpr (!EMIT && T0 <= kLeafTier) {
+        // (a frame of a wider tier never comes as a leaf step: k_deep_count sends it the old way)
+        if (kind == kStepLeaf) {
+          leaf_step<T0, MAXT>(a, st, L, top, lf, lane, acc);
+          return;
+        }
+      }
+      if (kind == kStepRow)
         row_step<T0, MAXT, EMIT>(a, fst, st, L, top, stack, lane, acc);
       else
         batch_step<T0, MAXT, EMIT>(a, fst, st, L, top, lf, stack, lane, acc);
@@ -859,7 +1042,7 @@ __device__ __forceinline__ void step_tier(unsigned wt, bool row_mode, const Deep
     }
   }
   if constexpr (sizeof...(Ts) > 0)
-    step_tier<MAXT, EMIT, Ts...>(wt, row_mode, a, fst, st, L, top, lf, stack, lane, acc);
+    step_tier<MAXT, EMIT, Ts...>(wt, kind, a, fst, st, L, top, lf, stack, lane, acc);
 }
 
 // waves per SIMD the count kernel is compiled for by default (blocks_per_cu may select the other
@@ -881,6 +1064,7 @@ __global__ __launch_bounds__(256, WPS) __attribute__((amdgpu_waves_per_eu(WPS)))
                         a.stacks + gw * a.stack_bytes, a.stacks0 ? a.seg0 : 0ull};
 
   for (int d = lane; d < 64; d += 64) L.depth_cnt[d] = 0;
+  if (lane == 0) L.leaf_cands = 0;
   WaveAcc acc{0, 0, 0, 0, 0};
   __builtin_amdgcn_wave_barrier();
 
@@ -1041,12 +1225,19 @@ __global__ __launch_bounds__(256, WPS) __attribute__((amdgpu_waves_per_eu(WPS)))
       const unsigned long long pairs = (unsigned long long)m * (m - 1) / 2;
       const bool row_mode = (top.meta & kSingle) || meta_lead(top.meta) ||
                             pairs > (unsigned long long)kCap;
+      // leaf step (count-only, leaf_m > 0): a plain class of 2..leaf_m members in a block of a
+      // tier <= kLeafTier; a wider block's frames take the row / batch path as before.  Decided
+      // before the room check: a leaf step writes nothing, so it needs no stack or frame room.
+      const bool leaf_mode = !EMIT && !row_mode && m >= 2u && m <= a.leaf_m &&
+                             wt <= (unsigned)kLeafTier;
       const unsigned long long need =
           (unsigned long long)(wt + 1 + E) * roundup16(row_mode ? m : kCap) * 8ull;
       const unsigned long long top_at =  // (a block never straddles the two stack parts)
           (st.mem_top < stack.n0 && st.mem_top + need > stack.n0) ? stack.n0 : st.mem_top;
-      if (top_at + need > stack.n0 + a.stack_bytes || st.nf + kCap + 2 > (unsigned)a.fcap ||
-          st.nb + 1 >= (unsigned)kBStack || (!a.steal && acc.budget_used >= a.budget)) {
+      const bool no_room = !leaf_mode &&
+                           (top_at + need > stack.n0 + a.stack_bytes ||
+                            st.nf + kCap + 2 > (unsigned)a.fcap || st.nb + 1 >= (unsigned)kBStack);
+      if (no_room || (!a.steal && acc.budget_used >= a.budget)) {
         if (spill_frames<MAXT, EMIT>(a, fst, st, L, lane, false, st.nf,
                                      a.split_q ? (long long)task_ticket : -1ll) < 0)
           failed = true;
@@ -1088,8 +1279,9 @@ __global__ __launch_bounds__(256, WPS) __attribute__((amdgpu_waves_per_eu(WPS)))
         failed = true;
         break;
       }
-      step_tier<MAXT, EMIT, 1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64>(wt, row_mode, a, fst, st, L, top,
-                                                               lf, stack, lane, acc);
+      step_tier<MAXT, EMIT, 1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64>(
+          wt, leaf_mode ? kStepLeaf : row_mode ? kStepRow : kStepBatch, a, fst, st, L, top, lf, stack,
+          lane, acc);
       free_blocks(L, st);
     }
     if (tr && !failed && lane == 0) {
@@ -1141,6 +1333,7 @@ __global__ __launch_bounds__(256, WPS) __attribute__((amdgpu_waves_per_eu(WPS)))
     atomicXor(&a.ctl->digest_xor, acc.dxor);
     atomicAdd(&a.ctl->candidates, acc.cands);
     atomicAdd(&a.ctl->chunks, acc.chunks);
+    if (L.leaf_cands) atomicAdd(&a.ctl->leaf_candidates, L.leaf_cands);
   }
   for (int d = lane; d < 64; d += 64)
     if (L.depth_cnt[d]) atomicAdd(&a.ctl->per_depth[d], L.depth_cnt[d]);
@@ -1538,6 +1731,7 @@ int deep_waves_per_simd(int maxt) {
 int deep_waves_per_block() { return kWaves; }
 int deep_min_fcap() { return kCap + 64; }
 int deep_node_chunk() { return (int)kNodeChunk; }
+int deep_leaf_max() { return kLeafMax; }
 
 size_t deep_row_block_bytes(int W, int64_t m, int extra) {
   return (size_t)(W + 1 + extra) * (size_t)roundup16((unsigned long long)std::max<int64_t>(m, kCap)) * 8;

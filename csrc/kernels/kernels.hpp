@@ -17,8 +17,9 @@ struct DeepFrame {  // one class: members P ∪ {x_k}, k in [s0, s0 + m), of a w
   unsigned pad;             // slot stride (multiple of 16)
   unsigned s0;              // first member slot
   unsigned m;               // members
-  unsigned meta;            // bits 0-7 |P|, bit 8 single (expand member s0 only), 9-15 block
-                            // width (words), 16-31 block index
+  unsigned meta;            // bits 0-5 |P|, bit 6 single (expand member s0 only), 7-13 block
+                            // width (words), 14-20 block-stack index + 1 (0 = external), 21-31
+                            // lead (first members still to expand, 0 = all): deep.hip make_meta
 };
 static_assert(sizeof(DeepFrame) == 32, "DeepFrame is read as 8 dwords");
 struct DeepCtl {  // per-round control + accumulated results (zeroed once per call)
@@ -30,12 +31,15 @@ struct DeepCtl {  // per-round control + accumulated results (zeroed once per ca
   unsigned long long node_top;    // emit mode: node ids handed out (chunks; keeps counting past
                                   // the arena's capacity, so the host learns the size it needs)
   unsigned long long digest_sum, digest_xor;
-  unsigned long long candidates, chunks;
+  unsigned long long candidates, chunks;  // candidates: AND+popcount evaluations.  A leaf step
+                                  // evaluates every subset of its class, also those whose
+                                  // sub-subset already failed, so this may exceed the DFS's count
   unsigned long long per_depth[64];
   unsigned error;                 // bit 0 out queue full, bit 1 heap full, bit 2 timeout,
                                   // bit 3 a frame of an uninstantiated width
   unsigned pad_[3];
   unsigned long long t_drain;     // (trace) wall clock when the last queued task was dequeued
+  unsigned long long leaf_candidates;  // subsets evaluated by leaf steps (part of `candidates`)
 };
 struct DeepArgs {
   const DeepFrame* in;
@@ -55,6 +59,8 @@ struct DeepArgs {
   unsigned minsup;
   unsigned long long budget;      // 64-lane passes per task before it spills
   int max_len;                    // 0 = all sizes
+  unsigned leaf_m;                // count-only: a plain class of 2..leaf_m members is finished in
+                                  // one leaf step (0 = off; <= deep_leaf_max())
   unsigned split_min;             // spilled frames above this many members split per member
   unsigned long long timeout_ticks;  // wall_clock64 ticks a wave may run (then error bit 2)
   // steal mode (one launch, no rounds): out == in, spilled tasks are appended at in[n_in + k]
@@ -109,6 +115,7 @@ int deep_waves_per_simd(int maxt);  // its default occupancy (and blocks per CU)
 int deep_count_wps(int maxt, int want, bool emit = false);  // instance occupancy: `want` if instantiated
 int deep_waves_per_block();
 int deep_min_fcap();
+int deep_leaf_max();    // largest DeepArgs::leaf_m the count kernel is built for
 int deep_node_chunk();  // emit mode: node ids a wave takes at a time
 size_t deep_row_block_bytes(int W, int64_t m, int extra = 0);  // stack room of a step over m members
                                                                // (extra: emit mode's node row)
