@@ -140,6 +140,8 @@ namespace emu {
 inline void wave_barrier() { tl->wave->barrier(); }
 }  // namespace emu
 #define __builtin_amdgcn_wave_barrier() emu::wave_barrier()
+// memory fences of any order and scope: the lane threads' accesses are made sequentially consistent
+#define __builtin_amdgcn_fence(order, scope) __atomic_thread_fence(__ATOMIC_SEQ_CST)
 
 inline unsigned __shfl(unsigned v, int src, int = 64) { return (unsigned)emu::xchg(v, src); }
 inline int __shfl(int v, int src, int = 64) { return (int)emu::xchg((uint32_t)v, src); }
@@ -149,6 +151,7 @@ inline long long __shfl(long long v, int src, int = 64) {
 inline unsigned long long __shfl(unsigned long long v, int src, int = 64) {
   return emu::xchg(v, src);
 }
+inline long __shfl(long v, int src, int = 64) { return (long)emu::xchg((uint64_t)v, src); }
 inline void __syncthreads() { emu::tl->block->barrier(); }
 namespace emu {
 inline void* dyn_lds() { return tl->block->dyn.data(); }

@@ -291,6 +291,20 @@ PYBIND11_MODULE(_native, m) {
      py::arg("metric") = 0, py::arg("min_threshold") = 0.8, py::arg("max_antecedent") = 0,
      py::arg("threads") = 0);
 
+  // ---------------- closed / maximal itemsets ----------------
+  m.def("itemset_flags", [](I64 parent, I32 item, py::array_t<uint32_t, py::array::c_style | py::array::forcecast> count,
+                            U8 depth, int threads) {
+    const int64_t n = item.size();
+    KMLS_CHECK(parent.size() == n && count.size() == n && depth.size() == n, "trie arrays differ in size");
+    py::array_t<uint8_t> flags((py::ssize_t)n);
+    uint8_t* pf = flags.mutable_data();
+    {
+      py::gil_scoped_release nogil;
+      itemset_flags(parent.data(), item.data(), count.data(), depth.data(), n, pf, threads);
+    }
+    return flags;
+  }, py::arg("parent"), py::arg("item"), py::arg("count"), py::arg("depth"), py::arg("threads") = 0);
+
   // ---------------- CPU matcher ----------------
   py::class_<RuleIndex, std::shared_ptr<RuleIndex>>(m, "RuleIndex")
       .def(py::init([](int64_t n_items, I64 row_ptr, I32 cons, F64 score, U8 is_key) {

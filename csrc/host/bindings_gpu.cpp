@@ -141,6 +141,23 @@ void register_gpu_bindings(py::module_& m) {
      py::arg("metric") = 0, py::arg("min_threshold") = 0.8, py::arg("max_antecedent") = 0,
      py::arg("device") = 0);
 
+  m.def("itemset_flags_gpu", [](I64 parent, I32 item, U32 count, U8 depth, int device) {
+    const int64_t n = item.size();
+    KMLS_CHECK(parent.size() == n && count.size() == n && depth.size() == n, "trie arrays differ in size");
+    py::array_t<uint8_t> flags((py::ssize_t)n);
+    uint8_t* pf = flags.mutable_data();
+    double ms = 0;
+    {
+      py::gil_scoped_release nogil;
+      gpu::itemset_flags_gpu(device, parent.data(), item.data(), count.data(), depth.data(), n, pf,
+                             &ms);
+    }
+    py::dict d;
+    d["flags"] = flags;
+    d["kernel_ms"] = ms;
+    return d;
+  }, py::arg("parent"), py::arg("item"), py::arg("count"), py::arg("depth"), py::arg("device") = 0);
+
   m.def("group_to_csr_gpu", [](I32 keys, I32 vals, int32_t n_keys, bool dedup, int device) {
     KMLS_CHECK(keys.size() == vals.size(), "keys/vals differ in size");
     CSR g;
@@ -592,6 +609,20 @@ void register_gpu_bindings(py::module_& m) {
         d["n"] = n;
         return d;
       }, py::arg("min_depth") = 1, py::arg("base") = 0)
+      .def("deep_trie_flags", [](gpu::GpuMiner& g) {
+        const int64_t n = g.deep_trie_nodes();
+        py::array_t<uint8_t> flags((py::ssize_t)n);
+        uint8_t* pf = flags.mutable_data();
+        double ms = 0;
+        {
+          py::gil_scoped_release nogil;
+          g.deep_trie_flags(pf, &ms);
+        }
+        py::dict d;
+        d["flags"] = flags;
+        d["kernel_ms"] = ms;
+        return d;
+      })
       .def("synchronize", &gpu::GpuMiner::synchronize, py::call_guard<py::gil_scoped_release>());
 
   py::class_<gpu::GpuRuleIndex, std::shared_ptr<gpu::GpuRuleIndex>>(m, "GpuRuleIndex")

@@ -261,6 +261,7 @@ int64_t GpuMiner::deep_arena_trie(int min_depth, int64_t base, bool* item16) {
   kern::deep_trie_scatter(b.n_parent, b.n_item, b.n_count, b.n_depth, n, b.t_new_id, d_ids_, base,
                           b.t_parent, b.t_item, b.t_item16, b.t_count, b.t_depth, s);
   b.t_n = m;
+  b.t_whole = min_depth <= 1 && base == 0;
   if (item16) *item16 = b.t_item16;
   return m;
 }
@@ -276,6 +277,52 @@ void GpuMiner::deep_trie_download(int32_t* parent, void* item, uint16_t* count, 
   KMLS_HIP(hipMemcpyAsync(count, b.t_count, m * 2, hipMemcpyDeviceToHost, s));
   KMLS_HIP(hipMemcpyAsync(depth, b.t_depth, m, hipMemcpyDeviceToHost, s));
   KMLS_HIP(hipStreamSynchronize(s));
+}
+
+int64_t GpuMiner::deep_trie_nodes() const { return deep_ ? deep_->t_n : 0; }
+
+void GpuMiner::deep_trie_flags(uint8_t* out, double* kernel_ms) {
+  KMLS_CHECK(deep_ && deep_->t_parent != nullptr && deep_->t_n >= 0,
+             "deep_trie_flags: deep_arena_trie first");
+  KMLS_CHECK(deep_->t_whole,
+             "deep_trie_flags: the device trie is a partial export (min_depth > 1 or base > 0); "
+             "a rank's share is not closed under subsets");
+  KMLS_HIP(hipSetDevice(device_));
+  hipStream_t s = (hipStream_t)stream_;
+  DeepBufs& b = *deep_;
+  const int64_t n = b.t_n;
+  if (n == 0) return;
+  KMLS_CHECK(n < (1ll << 31) - 1, "deep_trie_flags: trie larger than 2^31 nodes");
+  const uint64_t cap = kern::closed_hash_slots(n);
+  struct Buf {  // freed on every way out
+    void* p = nullptr;
+    ~Buf() { if (p) (void)hipFree(p); }
+  } keys, vals, flags, eq, err;
+  KMLS_HIP(hipMalloc(&keys.p, cap * 8));
+  KMLS_HIP(hipMalloc(&vals.p, cap * 4));
+  KMLS_HIP(hipMalloc(&flags.p, std::max<size_t>((size_t)n, 256)));
+  KMLS_HIP(hipMalloc(&eq.p, std::max<size_t>((size_t)n, 256)));
+  KMLS_HIP(hipMalloc(&err.p, 256));
+  const kern::ClosedScratch x{(unsigned long long*)keys.p, (int32_t*)vals.p, cap - 1,
+                              (unsigned char*)flags.p, (unsigned char*)eq.p, (unsigned int*)err.p};
+  hipEvent_t e0, e1;
+  KMLS_HIP(hipEventCreate(&e0));
+  KMLS_HIP(hipEventCreate(&e1));
+  struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } eg{e0, e1};
+  KMLS_HIP(hipEventRecord(e0, s));
+  kern::closed_flags_narrow(b.t_parent, b.t_item, b.t_item16, b.t_count, b.t_depth, n, x, n_cus_, s);
+  KMLS_HIP(hipEventRecord(e1, s));
+  unsigned int e = 0;
+  KMLS_HIP(hipMemcpyAsync(&e, x.error, 4, hipMemcpyDeviceToHost, s));
+  KMLS_HIP(hipMemcpyAsync(out, x.flags, (size_t)n, hipMemcpyDeviceToHost, s));
+  KMLS_HIP(hipStreamSynchronize(s));
+  KMLS_CHECK(e == 0, "GPU itemset flags: a subset of a frequent itemset is missing from the trie "
+                     "(trie not closed under subsets, or itemset longer than 63)");
+  if (kernel_ms) {
+    float ms = 0.f;
+    KMLS_HIP(hipEventElapsedTime(&ms, e0, e1));
+    *kernel_ms = ms;
+  }
 }
 
 }  // namespace gpu

@@ -75,6 +75,7 @@ struct DeepBufs {
   int64_t tr_cap = 0, t_ids_cap = 0;
   int64_t t_n = 0;               // nodes of the last layout
   bool t_item16 = true;
+  bool t_whole = false;          // the last layout was the whole trie (min_depth 1, base 0)
   int64_t* d_split_q = nullptr;   // pre-split layout: queue slot and heap offset per heavy task
   int64_t* d_split_heap = nullptr;
   int64_t split_cap = 0;

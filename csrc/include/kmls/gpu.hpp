@@ -308,6 +308,12 @@ class GpuMiner {
   // i32, support u16, size u8) to host memory.
   int64_t deep_arena_trie(int min_depth, int64_t base, bool* item16);
   void deep_trie_download(int32_t* parent, void* item, uint16_t* count, uint8_t* depth);
+  // Closed / maximal flags (kern::closed_flags_narrow) of the trie the last
+  // deep_arena_trie(min_depth = 1, base = 0) left on the device: t_n bytes to `out`, nothing
+  // else crosses the bus.  Refuses after a partial export (min_depth > 1 or base > 0): a rank's
+  // share is not closed under subsets.  kernel_ms (optional) = hash build + marks + fold.
+  void deep_trie_flags(uint8_t* out, double* kernel_ms = nullptr);
+  int64_t deep_trie_nodes() const;  // nodes of the last deep_arena_trie (0 before the first)
 
   // Frequent items of the last select(): ids (ascending support) and counts.
   const FrequentItems& frequent() const { return fi_; }
@@ -473,6 +479,13 @@ RuleSet association_rules_gpu(int device, const int64_t* parent, const int32_t* 
                               const uint32_t* count, const uint8_t* depth, int64_t n, int64_t n_tx,
                               RuleMetric metric, double min_threshold, int max_antecedent,
                               double* kernel_ms);
+
+// Closed / maximal flags of a host trie on the GPU (closed_gpu.hip / kernels/closed.hip): the
+// bytes itemset_flags writes, same errors.  kernel_ms (optional) = hash build + marks + fold,
+// without the upload.
+void itemset_flags_gpu(int device, const int64_t* parent, const int32_t* item,
+                       const uint32_t* count, const uint8_t* depth, int64_t n, uint8_t* flags_out,
+                       double* kernel_ms);
 
 // Transaction builder on the GPU (kernels/groupby.hip): same CSR as group_to_csr(dedup,
 // sort_rows=true).

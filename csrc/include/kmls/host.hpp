@@ -110,6 +110,18 @@ RuleSet association_rules_cpu(const int64_t* parent, const int32_t* item, const 
                               RuleMetric metric, double min_threshold, int max_antecedent,
                               int threads);
 
+// ---- closed / maximal itemsets (closed_cpu.cpp) ---------------------------------------------
+// One byte per node of a trie that is closed under subsets: bit 0 CLOSED (no proper superset in
+// the trie has the same count), bit 1 MAXIMAL (no proper superset in the trie).  Flags are
+// relative to the trie given: under max_len, an itemset of the cap size has no superset in the
+// trie and is reported closed and maximal.  Throws if parents do not precede their children, a
+// path is longer than 63, or a subset of a node is missing.  CPU twin of gpu::itemset_flags_gpu.
+constexpr uint8_t kItemsetClosed = 1, kItemsetMaximal = 2;
+void validate_trie_shape(const int64_t* parent, const uint8_t* depth, int64_t n_nodes,
+                         const char* who);
+void itemset_flags(const int64_t* parent, const int32_t* item, const uint32_t* count,
+                   const uint8_t* depth, int64_t n_nodes, uint8_t* flags_out, int threads);
+
 // ---- CPU matcher ---------------------------------------------------------------------------
 // Rule index: for each key item, an ordered row of (consequent, score).  Rows may be empty
 // (frequent songs without pairs are keys with `{}`; rest_api/app/main.py:235 distinguishes

@@ -653,6 +653,27 @@ void rules_pass(const RuleArgs& a, int grid, hipStream_t s);
 size_t rules_scan_temp_bytes(int64_t n);
 void rules_scan(const int64_t* in, int64_t* out, int64_t n, void* tmp, size_t tb, hipStream_t s);
 
+// ---- closed / maximal itemset flags (closed.hip) ----
+constexpr unsigned char kFlagClosed = 1;   // no proper superset in the trie has the same count
+constexpr unsigned char kFlagMaximal = 2;  // no proper superset in the trie
+struct ClosedScratch {        // device buffers of one call (cleared by it)
+  unsigned long long* keys;   // [mask + 1] node hash (closed_hash_slots(n) slots)
+  int32_t* vals;              // [mask + 1]
+  unsigned long long mask;
+  unsigned char* flags;       // [n] "has a superset" marks, then the result
+  unsigned char* eq;          // [n] "has an equal-support superset" marks
+  unsigned int* error;        // 0, 1 = a subset is missing from the trie, 2 = a path above 63
+};
+uint64_t closed_hash_slots(int64_t n);  // power of two >= 2n (load factor <= 0.5)
+// one flag byte per node of a trie closed under subsets (n < 2^31 - 1), asynchronous on s: the
+// host trie's widths (hash built by rules_hash_build) and the device-resident deep trie's
+void closed_flags(const int64_t* parent, const int32_t* item, const uint32_t* count,
+                  const unsigned char* depth, int64_t n, const ClosedScratch& x, int n_cus,
+                  hipStream_t s);
+void closed_flags_narrow(const int32_t* parent, const void* item, bool item16,
+                         const uint16_t* count, const unsigned char* depth, int64_t n,
+                         const ClosedScratch& x, int n_cus, hipStream_t s);
+
 // ---- transaction builder (groupby.hip) ----
 // CSR of vals grouped by keys in [0, n_keys): rows sorted (and duplicate-free when dedup).
 // Returns nnz (synchronises the stream).

@@ -23,6 +23,7 @@
 #include <string>
 
 #include "kernels.hpp"
+#include "trie_hash.hpp"
 
 #define KMLS_HIP(expr)                                                                  \
   do {                                                                                  \
@@ -40,17 +41,7 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr int kLdsBits = 12;                 // LDS subset table: 4096 int32 per wave
-constexpr unsigned long long kEmpty = ~0ull;
-
-__device__ __forceinline__ unsigned long long hkey(int64_t parent, int32_t item) {
-  return ((unsigned long long)(parent + 1) << 32) | (unsigned long long)(uint32_t)item;
-}
-__device__ __forceinline__ unsigned long long hmix(unsigned long long k) {
-  k ^= k >> 33;
-  k *= 0xFF51AFD7ED558CCDull;
-  k ^= k >> 33;
-  return k;
-}
+constexpr unsigned long long kEmpty = kTrieHashEmpty;
 
 __global__ void k_hash_build(const int64_t* __restrict__ parent, const int32_t* __restrict__ item,
                              int64_t n, unsigned long long* __restrict__ keys,
@@ -67,19 +58,6 @@ __global__ void k_hash_build(const int64_t* __restrict__ parent, const int32_t* 
       }
       h = (h + 1) & mask;
     }
-  }
-}
-
-__device__ __forceinline__ int32_t hlookup(const unsigned long long* __restrict__ keys,
-                                           const int32_t* __restrict__ vals,
-                                           unsigned long long mask, int32_t parent, int32_t item) {
-  const unsigned long long k = hkey(parent, item);
-  unsigned long long h = hmix(k) & mask;
-  while (true) {
-    const unsigned long long kk = keys[h];
-    if (kk == k) return vals[h];
-    if (kk == kEmpty) return -2;
-    h = (h + 1) & mask;
   }
 }
 

@@ -48,6 +48,7 @@ class JobSettings:
     checkpoint_dir: Optional[pathlib.Path] = None  # KMLS_CHECKPOINT_DIR: phase resume
     dist_timeout_s: float = 600.0      # KMLS_DIST_TIMEOUT_S: process-group init + collectives
     sweep_timeout_s: float = 86400.0   # KMLS_SWEEP_TIMEOUT_S: ranks waiting for rank 0's sweep
+    itemset_flags: bool = False        # ITEMSET_FLAGS: closed / maximal byte per saved itemset
 
     DIST_MODES = ("auto", "deep", "tx", "item", "shard", "replicate")
 
@@ -97,6 +98,7 @@ class JobSettings:
                             if os.environ.get("KMLS_CHECKPOINT_DIR") else None),
             dist_timeout_s=float(_env("KMLS_DIST_TIMEOUT_S", "600")),
             sweep_timeout_s=float(_env("KMLS_SWEEP_TIMEOUT_S", "86400")),
+            itemset_flags=_env("ITEMSET_FLAGS", "false").lower() in ("1", "true", "yes"),
         )
 
 

@@ -65,7 +65,7 @@ def mine_rules(cfg: JobSettings, tx: pp.PlaylistTransactions, min_support: float
     backend = backend or (default_backend() if cfg.miner == "auto" else cfg.miner)
     trie = mine_csr(tx.tx_ptr, tx.items, len(tx.names), min_support, backend=backend,
                     pairs_only=(cfg.rules_mode == "pairs"), columns=tx.names,
-                    rule_index=(backend == "gpu"))
+                    rule_index=(backend == "gpu"), flags=cfg.itemset_flags)
     dev_map = trie.stats.pop("device_rule_map", None) if isinstance(trie.stats, dict) else None
     if dev_map is not None:
         idx = index_from_device_csr(dev_map, len(tx.names), trie.item[trie.depth == 1], tx.n_tx,
@@ -340,16 +340,23 @@ def run_support_sweep(cfg: JobSettings, tx: pp.PlaylistTransactions, total_songs
 def save_itemsets(cfg: JobSettings, trie: ItemsetTrie) -> None:
     """``frequent_itemsets.npz``: the trie arrays as mined (narrow widths kept: 9 B per itemset
     from the GPU miners), streamed into the temp file of the atomic write — at ds1 @0.02 that
-    is 1.4e9 itemsets, so no in-memory copy of the archive is made."""
+    is 1.4e9 itemsets, so no in-memory copy of the archive is made.  ITEMSET_FLAGS adds
+    ``flags``: one byte per itemset, bit 0 closed, bit 1 maximal (``ItemsetTrie.flags``)."""
+    extra = {"flags": trie.flags()} if cfg.itemset_flags else {}
+
     def write(f):
         np.savez(f, parent=trie.parent, item=trie.item, count=trie.count, depth=trie.depth,
-                 n_tx=np.int64(trie.n_tx), min_support=np.float64(trie.min_support))
+                 n_tx=np.int64(trie.n_tx), min_support=np.float64(trie.min_support), **extra)
     atomic_write_with(cfg.pickles_folder / ITEMSETS_FILE, write)
 
 
 def run(cfg: Optional[JobSettings] = None) -> Dict:
     cfg = cfg or JobSettings.from_env()
     distributed = cfg.num_gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) > 1
+    if cfg.itemset_flags and distributed:
+        # the flags need one trie that is closed under subsets; the ranks' sub-tries are not
+        raise RuntimeError("ITEMSET_FLAGS is not supported by the multi-GPU job modes: "
+                           "run the job on one GPU (or MINER=cpu) to save closed / maximal flags")
     rank = 0
     side = None  # gloo group for long host-side waits (the sweep), off the RCCL watchdog
     if distributed:

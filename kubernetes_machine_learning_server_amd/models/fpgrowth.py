@@ -23,8 +23,16 @@ import numpy as np
 from ..ops import native
 from . import oracle as _oracle
 
-__all__ = ["TransactionEncoder", "ItemsetTrie", "fpgrowth", "mine_csr", "csr_from_lists",
-           "default_backend", "full_miner"]
+__all__ = ["TransactionEncoder", "ItemsetTrie", "fpgrowth", "fpmax", "fpclose", "mine_csr",
+           "csr_from_lists", "default_backend", "full_miner"]
+
+FLAG_CLOSED = 1   # no proper superset among the trie's itemsets has the same support
+FLAG_MAXIMAL = 2  # no proper superset among the trie's itemsets
+# ItemsetTrie.flags(backend="auto") uploads the trie to the GPU from this many itemsets on.
+# Measured (profiles/closed_flags.md): at 18,624 itemsets the CPU twin still wins (1.0 ms against
+# 1.8 ms for itemset_flags_gpu, upload included); 77,905 is the first measured size where the GPU
+# wins (2.4 ms against 2.8 ms), and the two straight lines through those points cross near 61,000
+FLAGS_GPU_MIN_NODES = 75_000
 
 
 # --------------------------------------------------------------------------------------------
@@ -76,9 +84,43 @@ class ItemsetTrie:
     min_support: float
     stats: Dict = dataclasses.field(default_factory=dict)
     columns: Optional[Sequence] = None
+    _flags: Optional[np.ndarray] = dataclasses.field(default=None, repr=False, compare=False)
 
     def __len__(self) -> int:
         return int(len(self.item))
+
+    def flags(self, backend: str = "auto", device: int = 0) -> np.ndarray:
+        """One byte per itemset: bit 0 (``FLAG_CLOSED``) no proper superset in this trie has the
+        same support, bit 1 (``FLAG_MAXIMAL``) no proper superset is in this trie.  Computed once
+        and cached.  The flags are relative to the trie: mined with ``max_len``, an itemset of
+        the cap size has no superset here and is reported closed and maximal.
+
+        ``backend``: "gpu" (HIP kernel, csrc/kernels/closed.hip), "cpu" (threaded C++ twin, same
+        bytes), "auto" (GPU when one is visible and the trie is large enough to pay for the
+        upload).  Raises if a subset of an itemset is missing from the trie."""
+        if self._flags is None:
+            args = (np.ascontiguousarray(self.parent, np.int64),
+                    np.ascontiguousarray(self.item, np.int32),
+                    np.ascontiguousarray(self.count, np.uint32),
+                    np.ascontiguousarray(self.depth, np.uint8))
+            if backend == "auto":
+                backend = ("gpu" if (len(self) >= FLAGS_GPU_MIN_NODES and native.gpu_available())
+                           else "cpu")
+            if backend == "gpu":
+                self._flags = native.require_gpu().itemset_flags_gpu(*args, device)["flags"]
+            elif backend == "cpu":
+                self._flags = native.load().itemset_flags(*args)
+            else:
+                raise ValueError(f"unknown backend {backend!r}")
+        return self._flags
+
+    def closed_mask(self, backend: str = "auto") -> np.ndarray:
+        """Boolean mask of the closed itemsets (see :meth:`flags`)."""
+        return (self.flags(backend) & FLAG_CLOSED) != 0
+
+    def maximal_mask(self, backend: str = "auto") -> np.ndarray:
+        """Boolean mask of the maximal itemsets (see :meth:`flags`)."""
+        return (self.flags(backend) & FLAG_MAXIMAL) != 0
 
     @property
     def support(self) -> np.ndarray:
@@ -96,18 +138,27 @@ class ItemsetTrie:
     def as_dict(self) -> Dict[frozenset, int]:
         return {frozenset(s): c for c, s in self.itemsets()}
 
-    def to_records(self, use_colnames: bool = True) -> List[Tuple[float, frozenset]]:
+    def to_records(self, use_colnames: bool = True, mask: Optional[np.ndarray] = None
+                   ) -> List[Tuple[float, frozenset]]:
+        """(support, itemset) per node, trie order; ``mask`` (bool per node) selects nodes."""
         cols = self.columns
+        if mask is not None:
+            mask = np.asarray(mask, dtype=bool)
+            if mask.shape != (len(self),):
+                raise ValueError(f"mask must hold one bool per itemset ({len(self)})")
         out = []
-        for c, s in self.itemsets():
+        for n, (c, s) in enumerate(self.itemsets()):
+            if mask is not None and not mask[n]:
+                continue
             names = [cols[i] for i in s] if (use_colnames and cols is not None) else list(s)
             out.append((c / self.n_tx, frozenset(names)))
         return out
 
-    def to_dataframe(self, use_colnames: bool = True):
-        """mlxtend's result: DataFrame[support: float, itemsets: frozenset]."""
+    def to_dataframe(self, use_colnames: bool = True, mask: Optional[np.ndarray] = None):
+        """mlxtend's result: DataFrame[support: float, itemsets: frozenset]; ``mask`` (bool per
+        node, e.g. :meth:`closed_mask`) selects the rows."""
         import pandas as pd
-        recs = self.to_records(use_colnames)
+        recs = self.to_records(use_colnames, mask)
         return pd.DataFrame({"support": [r[0] for r in recs], "itemsets": [r[1] for r in recs]})
 
     def singles(self) -> Tuple[np.ndarray, np.ndarray]:
@@ -161,7 +212,7 @@ def full_miner(n_tx: int, pairs_only: bool = False) -> str:
     return "deep"
 
 
-def _mine_deep_trie(g, min_support: float, ml: int) -> Dict:
+def _mine_deep_trie(g, min_support: float, ml: int, flags: bool = False) -> Dict:
     """Every frequent itemset through the deep miner: emit mode writes each one as a node of an
     HBM arena inside the search, the arena is compacted into a parent-first trie on the device
     (kernels/deep_trie.hip) and copied out in narrow widths (9 B per itemset)."""
@@ -173,18 +224,24 @@ def _mine_deep_trie(g, min_support: float, ml: int) -> Dict:
     t2 = time.perf_counter()
     if int(t["n"]) != int(d["n_itemsets"]):
         raise RuntimeError(f"deep trie holds {t['n']} nodes for {d['n_itemsets']} itemsets")
+    fl = g.deep_trie_flags() if flags else None  # while the trie is still on the device
+    t3 = time.perf_counter()
     st = {"n_itemsets": int(d["n_itemsets"]), "n_frequent_items": int(d["n_frequent_items"]),
           "max_depth": int(d["max_depth"]), "per_level": list(d["per_level"]),
           "digest": d["digest"], "miner": "deep", "levels_path": "deep-emit",
           "deep_ms": round((t1 - t0) * 1e3, 3), "trie_ms": round((t2 - t1) * 1e3, 3)}
-    return {"parent": t["parent"], "item": t["item"], "count": t["count"], "depth": t["depth"],
-            "stats": st}
+    out = {"parent": t["parent"], "item": t["item"], "count": t["count"], "depth": t["depth"],
+           "stats": st}
+    if fl is not None:
+        st["flags_ms"] = round((t3 - t2) * 1e3, 3)
+        out["flags"] = fl["flags"]
+    return out
 
 
 def mine_csr(tx_ptr: np.ndarray, items: np.ndarray, n_items: int, min_support: float,
              max_len: Optional[int] = None, backend: str = "auto", pairs_only: bool = False,
              columns: Optional[Sequence] = None, mfma: bool = False,
-             rule_index: bool = False) -> ItemsetTrie:
+             rule_index: bool = False, flags: bool = False) -> ItemsetTrie:
     """Mine CSR transactions (rows duplicate-free, item ids in [0, n_items)).
 
     GPU backend: short-transaction data (n_tx <= 4096, the reference's datasets) is mined by the
@@ -193,7 +250,11 @@ def mine_csr(tx_ptr: np.ndarray, items: np.ndarray, n_items: int, min_support: f
     ``rule_index`` (GPU backend): the mining call also builds the rule map on the device
     (``pairs_to_csr``, rows ordered by score desc then consequent name when ``columns`` are
     given); it is returned as ``trie.stats["device_rule_map"]`` (absent if the device could not
-    build it, e.g. after a fallback, or on the CPU backends)."""
+    build it, e.g. after a fallback, or on the CPU backends).
+
+    ``flags``: also compute the closed / maximal byte of every itemset (:meth:`ItemsetTrie.flags`)
+    before returning.  The deep GPU path does it on the device-resident trie, right after the
+    trie is laid out and without uploading anything; the other paths call ``trie.flags()``."""
     if not (0.0 < min_support):
         raise ValueError("`min_support` must be a positive number within the interval `(0, 1]`. "
                          f"Got {min_support}.")
@@ -209,7 +270,10 @@ def mine_csr(tx_ptr: np.ndarray, items: np.ndarray, n_items: int, min_support: f
         recs = _oracle.fpgrowth_oracle(X, min_support, None, max_len)
         if pairs_only:
             recs = [r for r in recs if len(r[1]) <= 2]
-        return _trie_from_records(recs, n_tx, min_support, columns)
+        trie = _trie_from_records(recs, n_tx, min_support, columns)
+        if flags:
+            trie.flags()
+        return trie
     if backend == "cpu":
         r = native.load().mine_cpu(tx_ptr, items, int(n_items), float(min_support), ml, 0,
                                    bool(pairs_only))
@@ -231,7 +295,7 @@ def mine_csr(tx_ptr: np.ndarray, items: np.ndarray, n_items: int, min_support: f
                 # truncated at 2 items builds it on the device (its trie is not downloaded)
                 rm = g.mine(float(min_support), 2, False, False, True, False, False, True)
                 idx = rm.get("index")
-            r = _mine_deep_trie(g, min_support, ml)
+            r = _mine_deep_trie(g, min_support, ml, flags)
             if idx is not None:
                 r["index"] = idx
         else:
@@ -243,8 +307,11 @@ def mine_csr(tx_ptr: np.ndarray, items: np.ndarray, n_items: int, min_support: f
     st["backend"] = backend
     if rule_index and "index" in r:
         st["device_rule_map"] = r["index"]
-    return ItemsetTrie(r["parent"], r["item"], r["count"], r["depth"], n_tx, min_support, st,
-                       columns)
+    trie = ItemsetTrie(r["parent"], r["item"], r["count"], r["depth"], n_tx, min_support, st,
+                       columns, r.get("flags"))
+    if flags:
+        trie.flags()
+    return trie
 
 
 def _trie_from_records(recs, n_tx, ms, columns) -> ItemsetTrie:
@@ -265,7 +332,7 @@ def _trie_from_records(recs, n_tx, ms, columns) -> ItemsetTrie:
 
 def fpgrowth(df, min_support: float = 0.5, use_colnames: bool = False,
              max_len: Optional[int] = None, verbose: int = 0, backend: str = "auto",
-             as_trie: bool = False):
+             as_trie: bool = False, flags: bool = False):
     """Drop-in for ``mlxtend.frequent_patterns.fpgrowth`` on a one-hot bool DataFrame/array.
 
     Returns the mlxtend-shaped DataFrame (or the :class:`ItemsetTrie` if ``as_trie``).
@@ -286,7 +353,26 @@ def fpgrowth(df, min_support: float = 0.5, use_colnames: bool = False,
     np.add.at(ptr, rows + 1, 1)
     ptr = np.cumsum(ptr)
     trie = mine_csr(ptr, colsx.astype(np.int32), I, min_support, max_len, backend,
-                    columns=cols if use_colnames else None)
+                    columns=cols if use_colnames else None, flags=flags)
     if as_trie:
         return trie
     return trie.to_dataframe(use_colnames)
+
+
+def fpmax(df, min_support: float = 0.5, use_colnames: bool = False,
+          max_len: Optional[int] = None, verbose: int = 0, backend: str = "auto"):
+    """Drop-in for ``mlxtend.frequent_patterns.fpmax``: the maximal frequent itemsets (those with
+    no frequent superset), as DataFrame[support, itemsets].  With ``max_len`` the itemsets are
+    maximal among those of at most ``max_len`` items."""
+    trie = fpgrowth(df, min_support, use_colnames, max_len, verbose, backend, as_trie=True,
+                    flags=True)
+    return trie.to_dataframe(use_colnames, mask=trie.maximal_mask())
+
+
+def fpclose(df, min_support: float = 0.5, use_colnames: bool = False,
+            max_len: Optional[int] = None, verbose: int = 0, backend: str = "auto"):
+    """The closed frequent itemsets (no superset of equal support), from which every frequent
+    itemset's support can be recovered; same signature and result shape as :func:`fpmax`."""
+    trie = fpgrowth(df, min_support, use_colnames, max_len, verbose, backend, as_trie=True,
+                    flags=True)
+    return trie.to_dataframe(use_colnames, mask=trie.closed_mask())
