@@ -271,14 +271,14 @@ PYBIND11_MODULE(_native, m) {
   // ---------------- association rules ----------------
   m.def("association_rules", [](I64 parent, I32 item, py::array_t<uint32_t, py::array::c_style | py::array::forcecast> count,
                                 U8 depth, int64_t n_tx, int metric, double min_threshold,
-                                int max_antecedent, int threads) {
+                                int max_antecedent, int threads, int basis) {
     const int64_t n = item.size();
     KMLS_CHECK(parent.size() == n && count.size() == n && depth.size() == n, "trie arrays differ in size");
     RuleSet r;
     {
       py::gil_scoped_release nogil;
       r = association_rules_cpu(parent.data(), item.data(), count.data(), depth.data(), n, n_tx,
-                                (RuleMetric)metric, min_threshold, max_antecedent, threads);
+                                (RuleMetric)metric, min_threshold, max_antecedent, threads, basis);
     }
     py::dict d;
     d["itemset"] = to_array(std::move(r.itemset));
@@ -289,7 +289,7 @@ PYBIND11_MODULE(_native, m) {
     return d;
   }, py::arg("parent"), py::arg("item"), py::arg("count"), py::arg("depth"), py::arg("n_tx"),
      py::arg("metric") = 0, py::arg("min_threshold") = 0.8, py::arg("max_antecedent") = 0,
-     py::arg("threads") = 0);
+     py::arg("threads") = 0, py::arg("basis") = 0);
 
   // ---------------- closed / maximal itemsets ----------------
   m.def("itemset_flags", [](I64 parent, I32 item, py::array_t<uint32_t, py::array::c_style | py::array::forcecast> count,
@@ -303,6 +303,24 @@ PYBIND11_MODULE(_native, m) {
       itemset_flags(parent.data(), item.data(), count.data(), depth.data(), n, pf, threads);
     }
     return flags;
+  }, py::arg("parent"), py::arg("item"), py::arg("count"), py::arg("depth"), py::arg("threads") = 0);
+
+  m.def("itemset_condense", [](I64 parent, I32 item, py::array_t<uint32_t, py::array::c_style | py::array::forcecast> count,
+                               U8 depth, int threads) {
+    const int64_t n = item.size();
+    KMLS_CHECK(parent.size() == n && count.size() == n && depth.size() == n, "trie arrays differ in size");
+    py::array_t<uint8_t> flags((py::ssize_t)n);
+    py::array_t<int32_t> closure((py::ssize_t)n);
+    uint8_t* pf = flags.mutable_data();
+    int32_t* pc = closure.mutable_data();
+    {
+      py::gil_scoped_release nogil;
+      itemset_condense(parent.data(), item.data(), count.data(), depth.data(), n, pf, pc, threads);
+    }
+    py::dict d;
+    d["flags"] = flags;
+    d["closure"] = closure;
+    return d;
   }, py::arg("parent"), py::arg("item"), py::arg("count"), py::arg("depth"), py::arg("threads") = 0);
 
   // ---------------- CPU matcher ----------------

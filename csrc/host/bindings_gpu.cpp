@@ -119,7 +119,7 @@ void register_gpu_bindings(py::module_& m) {
 
   m.def("association_rules_gpu", [](I64 parent, I32 item, U32 count, U8 depth, int64_t n_tx,
                                     int metric, double min_threshold, int max_antecedent,
-                                    int device) {
+                                    int device, int basis) {
     const int64_t n = item.size();
     KMLS_CHECK(parent.size() == n && count.size() == n && depth.size() == n, "trie arrays differ in size");
     RuleSet r;
@@ -127,7 +127,8 @@ void register_gpu_bindings(py::module_& m) {
     {
       py::gil_scoped_release nogil;
       r = gpu::association_rules_gpu(device, parent.data(), item.data(), count.data(), depth.data(),
-                                     n, n_tx, (RuleMetric)metric, min_threshold, max_antecedent, &ms);
+                                     n, n_tx, (RuleMetric)metric, min_threshold, max_antecedent, &ms,
+                                     basis);
     }
     py::dict d;
     d["itemset"] = to_array(std::move(r.itemset));
@@ -139,7 +140,7 @@ void register_gpu_bindings(py::module_& m) {
     return d;
   }, py::arg("parent"), py::arg("item"), py::arg("count"), py::arg("depth"), py::arg("n_tx"),
      py::arg("metric") = 0, py::arg("min_threshold") = 0.8, py::arg("max_antecedent") = 0,
-     py::arg("device") = 0);
+     py::arg("device") = 0, py::arg("basis") = 0);
 
   m.def("itemset_flags_gpu", [](I64 parent, I32 item, U32 count, U8 depth, int device) {
     const int64_t n = item.size();
@@ -154,6 +155,26 @@ void register_gpu_bindings(py::module_& m) {
     }
     py::dict d;
     d["flags"] = flags;
+    d["kernel_ms"] = ms;
+    return d;
+  }, py::arg("parent"), py::arg("item"), py::arg("count"), py::arg("depth"), py::arg("device") = 0);
+
+  m.def("itemset_condense_gpu", [](I64 parent, I32 item, U32 count, U8 depth, int device) {
+    const int64_t n = item.size();
+    KMLS_CHECK(parent.size() == n && count.size() == n && depth.size() == n, "trie arrays differ in size");
+    py::array_t<uint8_t> flags((py::ssize_t)n);
+    py::array_t<int32_t> closure((py::ssize_t)n);
+    uint8_t* pf = flags.mutable_data();
+    int32_t* pc = closure.mutable_data();
+    double ms = 0;
+    {
+      py::gil_scoped_release nogil;
+      gpu::itemset_condense_gpu(device, parent.data(), item.data(), count.data(), depth.data(), n,
+                                pf, pc, &ms);
+    }
+    py::dict d;
+    d["flags"] = flags;
+    d["closure"] = closure;
     d["kernel_ms"] = ms;
     return d;
   }, py::arg("parent"), py::arg("item"), py::arg("count"), py::arg("depth"), py::arg("device") = 0);
@@ -609,20 +630,23 @@ void register_gpu_bindings(py::module_& m) {
         d["n"] = n;
         return d;
       }, py::arg("min_depth") = 1, py::arg("base") = 0)
-      .def("deep_trie_flags", [](gpu::GpuMiner& g) {
+      .def("deep_trie_flags", [](gpu::GpuMiner& g, bool generators, bool closure) {
         const int64_t n = g.deep_trie_nodes();
         py::array_t<uint8_t> flags((py::ssize_t)n);
+        py::array_t<int32_t> clo((py::ssize_t)(closure ? n : 0));
         uint8_t* pf = flags.mutable_data();
+        int32_t* pc = closure ? clo.mutable_data() : nullptr;
         double ms = 0;
         {
           py::gil_scoped_release nogil;
-          g.deep_trie_flags(pf, &ms);
+          g.deep_trie_flags(pf, &ms, generators || closure, pc);
         }
         py::dict d;
         d["flags"] = flags;
+        if (closure) d["closure"] = clo;
         d["kernel_ms"] = ms;
         return d;
-      })
+      }, py::arg("generators") = false, py::arg("closure") = false)
       .def("synchronize", &gpu::GpuMiner::synchronize, py::call_guard<py::gil_scoped_release>());
 
   py::class_<gpu::GpuRuleIndex, std::shared_ptr<gpu::GpuRuleIndex>>(m, "GpuRuleIndex")

@@ -9,6 +9,10 @@
 // subset is marked "has a superset", and "has an equal-support superset" when the counts tie;
 // the flags are the complement of the marks.  Work is split over threads by node block; the
 // marks are idempotent relaxed byte stores, so the result does not depend on the schedule.
+//
+// itemset_condense adds the generator bit (no immediate subset has the same count: the same tie,
+// marked at S) and closure ids: the tie lowers up[subset] to the smallest such S, and every node
+// then follows up[] to its end, the closed superset of equal support.
 #include <algorithm>
 #include <atomic>
 #include <string>
@@ -75,17 +79,35 @@ void validate_trie_shape(const int64_t* parent, const uint8_t* depth, int64_t n_
   }
 }
 
-void itemset_flags(const int64_t* parent, const int32_t* item, const uint32_t* count,
-                   const uint8_t* depth, int64_t n_nodes, uint8_t* flags_out, int threads) {
+namespace {
+
+constexpr uint32_t kNone = 0xFFFFFFFFu;
+
+// flags_out: two bits, or three when generators; closure_out (optional) needs generators
+void flags_impl(const int64_t* parent, const int32_t* item, const uint32_t* count,
+                const uint8_t* depth, int64_t n_nodes, uint8_t* flags_out, bool generators,
+                int32_t* closure_out, int threads) {
   if (n_nodes == 0) return;
   KMLS_CHECK(n_nodes < (1ll << 31) - 1, "itemset flags: trie larger than 2^31 nodes");
   validate_trie_shape(parent, depth, n_nodes, "itemset flags");
   ChildMap child(n_nodes);
   for (int64_t v = 0; v < n_nodes; ++v) child.put(parent[v], item[v], (int32_t)v);
   std::vector<uint8_t> sup((size_t)n_nodes, 0), eq((size_t)n_nodes, 0);
-  auto mark = [&](int64_t sub, uint32_t c) {
+  std::vector<uint8_t> gen(generators ? (size_t)n_nodes : 0, 0);
+  std::vector<uint32_t> up(closure_out ? (size_t)n_nodes : 0, kNone);
+  auto mark = [&](int64_t sub, int64_t s) {
     __atomic_store_n(&sup[(size_t)sub], (uint8_t)1, __ATOMIC_RELAXED);
-    if (count[sub] == c) __atomic_store_n(&eq[(size_t)sub], (uint8_t)1, __ATOMIC_RELAXED);
+    if (count[sub] != count[s]) return;
+    __atomic_store_n(&eq[(size_t)sub], (uint8_t)1, __ATOMIC_RELAXED);
+    if (!generators) return;
+    __atomic_store_n(&gen[(size_t)s], (uint8_t)1, __ATOMIC_RELAXED);
+    if (closure_out) {
+      uint32_t old = __atomic_load_n(&up[(size_t)sub], __ATOMIC_RELAXED);
+      while ((uint32_t)s < old &&
+             !__atomic_compare_exchange_n(&up[(size_t)sub], &old, (uint32_t)s, true,
+                                          __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
+      }
+    }
   };
   const int nth = (int)std::max<int64_t>(
       1, std::min<int64_t>(threads > 0 ? threads : default_threads(), (n_nodes + 4095) / 4096));
@@ -113,12 +135,12 @@ void itemset_flags(const int64_t* parent, const int32_t* item, const uint32_t* c
           v = parent[v];
         }
         anc[0] = -1;
-        mark(anc[k - 1], count[s]);  // dropping the last item: the parent
+        mark(anc[k - 1], s);  // dropping the last item: the parent
         for (int j = 0; j + 1 < k; ++j) {
           int64_t q = anc[j];
           for (int i = j + 1; i < k && q >= -1; ++i) q = child.get(q, path[i]);
           if (q < 0) bad = 1;
-          else mark(q, count[s]);
+          else mark(q, s);
         }
       }
     }
@@ -131,7 +153,39 @@ void itemset_flags(const int64_t* parent, const int32_t* item, const uint32_t* c
                        "(trie not closed under subsets, or itemset longer than 63)");
   for (int64_t v = 0; v < n_nodes; ++v)
     flags_out[v] = (uint8_t)((eq[(size_t)v] ? 0 : kItemsetClosed) |
-                             (sup[(size_t)v] ? 0 : kItemsetMaximal));
+                             (sup[(size_t)v] ? 0 : kItemsetMaximal) |
+                             (generators && !gen[(size_t)v] ? kItemsetGenerator : 0));
+  if (!closure_out) return;
+  next = 0;
+  auto resolve = [&]() {
+    while (true) {
+      const int64_t b0 = next.fetch_add(kBlock);
+      if (b0 >= n_nodes) break;
+      const int64_t b1 = std::min(n_nodes, b0 + kBlock);
+      for (int64_t v = b0; v < b1; ++v) {
+        uint32_t x = (uint32_t)v;  // each step adds an item: at most 63 steps
+        while (up[(size_t)x] != kNone) x = up[(size_t)x];
+        closure_out[v] = (int32_t)x;
+      }
+    }
+  };
+  pool.clear();
+  for (int t = 1; t < nth; ++t) pool.emplace_back(resolve);
+  resolve();
+  for (auto& th : pool) th.join();
+}
+
+}  // namespace
+
+void itemset_flags(const int64_t* parent, const int32_t* item, const uint32_t* count,
+                   const uint8_t* depth, int64_t n_nodes, uint8_t* flags_out, int threads) {
+  flags_impl(parent, item, count, depth, n_nodes, flags_out, false, nullptr, threads);
+}
+
+void itemset_condense(const int64_t* parent, const int32_t* item, const uint32_t* count,
+                      const uint8_t* depth, int64_t n_nodes, uint8_t* flags_out,
+                      int32_t* closure_out, int threads) {
+  flags_impl(parent, item, count, depth, n_nodes, flags_out, true, closure_out, threads);
 }
 
 }  // namespace kmls

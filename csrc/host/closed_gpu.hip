@@ -30,10 +30,13 @@ struct DevBuf {  // RAII hipMalloc
 };
 }  // namespace
 
-void itemset_flags_gpu(int device, const int64_t* parent, const int32_t* item,
-                       const uint32_t* count, const uint8_t* depth, int64_t n, uint8_t* flags_out,
-                       double* kernel_ms) {
-  trace::Range rg_("kmls.itemset_flags_gpu");
+namespace {
+
+// upload, one hash build, marks (with generators: three bits, and closure ids when closure_out),
+// fold and resolve; the flag bytes and the closure ids come back
+void flags_gpu(int device, const int64_t* parent, const int32_t* item, const uint32_t* count,
+               const uint8_t* depth, int64_t n, uint8_t* flags_out, bool generators,
+               int32_t* closure_out, double* kernel_ms) {
   if (kernel_ms) *kernel_ms = 0.0;
   if (n == 0) return;
   KMLS_CHECK(n < (1ll << 31) - 1, "GPU itemset flags: trie larger than 2^31 nodes");
@@ -50,15 +53,18 @@ void itemset_flags_gpu(int device, const int64_t* parent, const int32_t* item,
   KMLS_HIP(hipMemcpyAsync(d_dep.p, depth, n, hipMemcpyHostToDevice, s));
   const uint64_t cap = kern::closed_hash_slots(n);
   DevBuf d_keys(cap * 8), d_vals(cap * 4), d_flags(n), d_eq(n), d_err(256);
+  DevBuf d_gen(generators ? n : 0), d_up(closure_out ? n * 4 : 0);
   hipDeviceProp_t prop;
   KMLS_HIP(hipGetDeviceProperties(&prop, device));
   hipEvent_t e0, e1;
   KMLS_HIP(hipEventCreate(&e0));
   KMLS_HIP(hipEventCreate(&e1));
   struct EvGuard { hipEvent_t a, b; ~EvGuard() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } eg{e0, e1};
-  const kern::ClosedScratch x{d_keys.as<unsigned long long>(), d_vals.as<int32_t>(), cap - 1,
-                              d_flags.as<unsigned char>(), d_eq.as<unsigned char>(),
-                              d_err.as<unsigned int>()};
+  kern::ClosedScratch x{d_keys.as<unsigned long long>(), d_vals.as<int32_t>(), cap - 1,
+                        d_flags.as<unsigned char>(), d_eq.as<unsigned char>(),
+                        d_err.as<unsigned int>()};
+  if (generators) x.gen = d_gen.as<unsigned char>();
+  if (closure_out) x.up = d_up.as<unsigned int>();
   KMLS_HIP(hipEventRecord(e0, s));
   kern::closed_flags(d_par.as<int64_t>(), d_item.as<int32_t>(), d_cnt.as<uint32_t>(),
                      d_dep.as<unsigned char>(), n, x, std::max(1, prop.multiProcessorCount), s);
@@ -66,6 +72,8 @@ void itemset_flags_gpu(int device, const int64_t* parent, const int32_t* item,
   unsigned int err = 0;
   KMLS_HIP(hipMemcpyAsync(&err, x.error, 4, hipMemcpyDeviceToHost, s));
   KMLS_HIP(hipMemcpyAsync(flags_out, x.flags, (size_t)n, hipMemcpyDeviceToHost, s));
+  if (closure_out)
+    KMLS_HIP(hipMemcpyAsync(closure_out, x.up, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   KMLS_HIP(hipStreamSynchronize(s));
   KMLS_CHECK(err == 0, "GPU itemset flags: a subset of a frequent itemset is missing from the trie "
                        "(trie not closed under subsets, or itemset longer than 63)");
@@ -74,6 +82,22 @@ void itemset_flags_gpu(int device, const int64_t* parent, const int32_t* item,
     KMLS_HIP(hipEventElapsedTime(&ms, e0, e1));
     *kernel_ms = ms;
   }
+}
+
+}  // namespace
+
+void itemset_flags_gpu(int device, const int64_t* parent, const int32_t* item,
+                       const uint32_t* count, const uint8_t* depth, int64_t n, uint8_t* flags_out,
+                       double* kernel_ms) {
+  trace::Range rg_("kmls.itemset_flags_gpu");
+  flags_gpu(device, parent, item, count, depth, n, flags_out, false, nullptr, kernel_ms);
+}
+
+void itemset_condense_gpu(int device, const int64_t* parent, const int32_t* item,
+                          const uint32_t* count, const uint8_t* depth, int64_t n,
+                          uint8_t* flags_out, int32_t* closure_out, double* kernel_ms) {
+  trace::Range rg_("kmls.itemset_condense_gpu");
+  flags_gpu(device, parent, item, count, depth, n, flags_out, true, closure_out, kernel_ms);
 }
 
 }  // namespace gpu

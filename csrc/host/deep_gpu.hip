@@ -281,7 +281,9 @@ void GpuMiner::deep_trie_download(int32_t* parent, void* item, uint16_t* count, 
 
 int64_t GpuMiner::deep_trie_nodes() const { return deep_ ? deep_->t_n : 0; }
 
-void GpuMiner::deep_trie_flags(uint8_t* out, double* kernel_ms) {
+void GpuMiner::deep_trie_flags(uint8_t* out, double* kernel_ms, bool generators,
+                               int32_t* closure_out) {
+  KMLS_CHECK(generators || closure_out == nullptr, "deep_trie_flags: closure ids need generators");
   KMLS_CHECK(deep_ && deep_->t_parent != nullptr && deep_->t_n >= 0,
              "deep_trie_flags: deep_arena_trie first");
   KMLS_CHECK(deep_->t_whole,
@@ -297,14 +299,22 @@ void GpuMiner::deep_trie_flags(uint8_t* out, double* kernel_ms) {
   struct Buf {  // freed on every way out
     void* p = nullptr;
     ~Buf() { if (p) (void)hipFree(p); }
-  } keys, vals, flags, eq, err;
+  } keys, vals, flags, eq, err, gen, up;
   KMLS_HIP(hipMalloc(&keys.p, cap * 8));
   KMLS_HIP(hipMalloc(&vals.p, cap * 4));
   KMLS_HIP(hipMalloc(&flags.p, std::max<size_t>((size_t)n, 256)));
   KMLS_HIP(hipMalloc(&eq.p, std::max<size_t>((size_t)n, 256)));
   KMLS_HIP(hipMalloc(&err.p, 256));
-  const kern::ClosedScratch x{(unsigned long long*)keys.p, (int32_t*)vals.p, cap - 1,
-                              (unsigned char*)flags.p, (unsigned char*)eq.p, (unsigned int*)err.p};
+  kern::ClosedScratch x{(unsigned long long*)keys.p, (int32_t*)vals.p, cap - 1,
+                        (unsigned char*)flags.p, (unsigned char*)eq.p, (unsigned int*)err.p};
+  if (generators) {
+    KMLS_HIP(hipMalloc(&gen.p, std::max<size_t>((size_t)n, 256)));
+    x.gen = (unsigned char*)gen.p;
+  }
+  if (closure_out) {
+    KMLS_HIP(hipMalloc(&up.p, std::max<size_t>((size_t)n * 4, 256)));
+    x.up = (unsigned int*)up.p;
+  }
   hipEvent_t e0, e1;
   KMLS_HIP(hipEventCreate(&e0));
   KMLS_HIP(hipEventCreate(&e1));
@@ -315,6 +325,8 @@ void GpuMiner::deep_trie_flags(uint8_t* out, double* kernel_ms) {
   unsigned int e = 0;
   KMLS_HIP(hipMemcpyAsync(&e, x.error, 4, hipMemcpyDeviceToHost, s));
   KMLS_HIP(hipMemcpyAsync(out, x.flags, (size_t)n, hipMemcpyDeviceToHost, s));
+  if (closure_out)
+    KMLS_HIP(hipMemcpyAsync(closure_out, x.up, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   KMLS_HIP(hipStreamSynchronize(s));
   KMLS_CHECK(e == 0, "GPU itemset flags: a subset of a frequent itemset is missing from the trie "
                      "(trie not closed under subsets, or itemset longer than 63)");

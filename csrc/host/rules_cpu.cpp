@@ -33,9 +33,15 @@ struct KeyHash {
 RuleSet association_rules_cpu(const int64_t* parent, const int32_t* item, const uint32_t* count,
                               const uint8_t* depth, int64_t n_nodes, int64_t n_tx,
                               RuleMetric metric, double min_threshold, int max_antecedent,
-                              int threads) {
+                              int threads, int basis) {
   RuleSet out;
   if (n_nodes == 0 || n_tx == 0) return out;
+  // min-max basis: closed itemsets, generator antecedents
+  std::vector<uint8_t> fl;
+  if (basis) {
+    fl.resize((size_t)n_nodes);
+    itemset_condense(parent, item, count, depth, n_nodes, fl.data(), nullptr, threads);
+  }
   // child map and root map
   std::unordered_map<std::pair<int64_t, int32_t>, int64_t, KeyHash> child;
   child.reserve((size_t)n_nodes * 2);
@@ -66,6 +72,7 @@ RuleSet association_rules_cpu(const int64_t* parent, const int32_t* item, const 
         const int k = depth[s];
         if (k < 2) continue;
         if (k > 30) { bad = true; continue; }
+        if (basis && !(fl[(size_t)s] & kItemsetClosed)) continue;
         path.assign((size_t)k, 0);
         int64_t v = s;
         for (int i = k - 1; i >= 0; --i) { path[(size_t)i] = item[v]; v = parent[v]; }
@@ -80,6 +87,7 @@ RuleSet association_rules_cpu(const int64_t* parent, const int32_t* item, const 
           const int64_t na = lookup(ante.data(), (int)ante.size());
           const int64_t nc = lookup(cons.data(), (int)cons.size());
           if (na < 0 || nc < 0) { bad = true; continue; }
+          if (basis && !(fl[(size_t)na] & kItemsetGenerator)) continue;
           const double sA = count[na] / T, sC = count[nc] / T;
           // exact count ratios (fpgrowth_py: getSupport(S) / getSupport(A)); a ratio of float
           // supports can land 1 ulp above an exactly-representable threshold

@@ -35,11 +35,13 @@ struct DevBuf {  // RAII hipMalloc
 RuleSet association_rules_gpu(int device, const int64_t* parent, const int32_t* item,
                               const uint32_t* count, const uint8_t* depth, int64_t n, int64_t n_tx,
                               RuleMetric metric, double min_threshold, int max_antecedent,
-                              double* kernel_ms) {
+                              double* kernel_ms, int basis) {
   trace::Range rg_("kmls.rules_gpu");
   RuleSet out;
   if (n == 0 || n_tx == 0) return out;
   KMLS_CHECK(n < (1ll << 31) - 1, "GPU rules: trie larger than 2^31 nodes");
+  // the flag kernel of the basis chases parent ids: they must stay inside the arrays
+  if (basis) validate_trie_shape(parent, depth, n, "GPU rules");
   KMLS_HIP(hipSetDevice(device));
   hipStream_t s;
   KMLS_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
@@ -93,6 +95,17 @@ RuleSet association_rules_gpu(int device, const int64_t* parent, const int32_t* 
   a.error = (unsigned int*)((char*)d_ctl.p + 16);
   a.pass = 0;
   a.nrules = d_nr.as<int64_t>();
+  // min-max basis: the three-bit flags from the arrays and the hash table already on the device
+  DevBuf d_flags(basis ? n : 0), d_eq(basis ? n : 0), d_gen(basis ? n : 0);
+  if (basis) {
+    kern::ClosedScratch x{d_keys.as<unsigned long long>(), d_vals.as<int32_t>(), cap - 1,
+                          d_flags.as<unsigned char>(), d_eq.as<unsigned char>(), a.error};
+    x.gen = d_gen.as<unsigned char>();
+    kern::closed_marks(a.parent, a.item, a.count, a.depth, n, x,
+                       std::max(1, prop.multiProcessorCount), s);
+    a.set_flags = d_flags.as<unsigned char>();
+    a.basis = 1;
+  }
   kern::rules_pass(a, grid, s);
   const size_t tb = kern::rules_scan_temp_bytes(n);
   DevBuf d_tmp(tb);

@@ -312,7 +312,11 @@ class GpuMiner {
   // deep_arena_trie(min_depth = 1, base = 0) left on the device: t_n bytes to `out`, nothing
   // else crosses the bus.  Refuses after a partial export (min_depth > 1 or base > 0): a rank's
   // share is not closed under subsets.  kernel_ms (optional) = hash build + marks + fold.
-  void deep_trie_flags(uint8_t* out, double* kernel_ms = nullptr);
+  // generators: the bytes also carry bit 2 (kern::kFlagGenerator); closure_out (t_n ids, needs
+  // generators): the closure id of every node.  Both computed where the trie lies; the extra
+  // device arrays exist only when asked for.
+  void deep_trie_flags(uint8_t* out, double* kernel_ms = nullptr, bool generators = false,
+                       int32_t* closure_out = nullptr);
   int64_t deep_trie_nodes() const;  // nodes of the last deep_arena_trie (0 before the first)
 
   // Frequent items of the last select(): ids (ascending support) and counts.
@@ -478,7 +482,10 @@ class GpuMiner {
 RuleSet association_rules_gpu(int device, const int64_t* parent, const int32_t* item,
                               const uint32_t* count, const uint8_t* depth, int64_t n, int64_t n_tx,
                               RuleMetric metric, double min_threshold, int max_antecedent,
-                              double* kernel_ms);
+                              double* kernel_ms, int basis = 0);
+// basis != 0: the min-max basis (see association_rules_cpu).  The closed / generator bits are
+// computed on the device from the uploaded arrays, through the rule engine's own hash table; no
+// flag byte crosses the bus.  kernel_ms then includes the flag kernels.
 
 // Closed / maximal flags of a host trie on the GPU (closed_gpu.hip / kernels/closed.hip): the
 // bytes itemset_flags writes, same errors.  kernel_ms (optional) = hash build + marks + fold,
@@ -486,6 +493,11 @@ RuleSet association_rules_gpu(int device, const int64_t* parent, const int32_t* 
 void itemset_flags_gpu(int device, const int64_t* parent, const int32_t* item,
                        const uint32_t* count, const uint8_t* depth, int64_t n, uint8_t* flags_out,
                        double* kernel_ms);
+// The three-bit bytes and closure ids of itemset_condense (closure_out may be null), same errors:
+// upload, one hash build, marks with generators, fold and resolve.
+void itemset_condense_gpu(int device, const int64_t* parent, const int32_t* item,
+                          const uint32_t* count, const uint8_t* depth, int64_t n,
+                          uint8_t* flags_out, int32_t* closure_out, double* kernel_ms);
 
 // Transaction builder on the GPU (kernels/groupby.hip): same CSR as group_to_csr(dedup,
 // sort_rows=true).

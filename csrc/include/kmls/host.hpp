@@ -108,7 +108,10 @@ struct RuleSet {  // rule r: antecedent node -> consequent node (trie ids), from
 RuleSet association_rules_cpu(const int64_t* parent, const int32_t* item, const uint32_t* count,
                               const uint8_t* depth, int64_t n_nodes, int64_t n_tx,
                               RuleMetric metric, double min_threshold, int max_antecedent,
-                              int threads);
+                              int threads, int basis = 0);
+// basis != 0: the min-max basis only — rules g -> S \ g with S flagged closed and g flagged
+// generator (itemset_condense's bits, computed inside); every other rule has the supports and
+// confidence of one of these.  Same filters, same order.
 
 // ---- closed / maximal itemsets (closed_cpu.cpp) ---------------------------------------------
 // One byte per node of a trie that is closed under subsets: bit 0 CLOSED (no proper superset in
@@ -121,6 +124,16 @@ void validate_trie_shape(const int64_t* parent, const uint8_t* depth, int64_t n_
                          const char* who);
 void itemset_flags(const int64_t* parent, const int32_t* item, const uint32_t* count,
                    const uint8_t* depth, int64_t n_nodes, uint8_t* flags_out, int threads);
+// The same two bits plus bit 2 GENERATOR (no immediate subset in the trie has the same count;
+// singletons always are) and, when closure_out is not null, closure ids: from v, step to the
+// smallest-id equal-count superset one item larger until there is none.  In a trie closed under
+// subsets and mined without a size cap that is the closed superset of equal support; under
+// max_len it is a closure relative to the trie.  closure_out[v] == v exactly when v is closed.
+// CPU twin of gpu::itemset_condense_gpu.
+constexpr uint8_t kItemsetGenerator = 4;
+void itemset_condense(const int64_t* parent, const int32_t* item, const uint32_t* count,
+                      const uint8_t* depth, int64_t n_nodes, uint8_t* flags_out,
+                      int32_t* closure_out, int threads);
 
 // ---- CPU matcher ---------------------------------------------------------------------------
 // Rule index: for each key item, an ordered row of (consequent, score).  Rows may be empty

@@ -25,6 +25,16 @@
 // mark), skipped when the byte already reads 1 — no atomics, and a stale read only repeats a
 // store of the same value.  k_closed_fold then turns the two arrays into the flag byte.
 // A subset that the trie lacks sets the error word (1), as does a path longer than 63 (2).
+//
+// GENERATOR (bit 2) is the dual of closed: no immediate subset has the same count.  The same
+// count tie that marks the subset "not closed" marks S "not a generator" (a third byte array, at
+// S, same discipline), so the generator variant of k_closed_mark (a compile-time bool; the
+// two-bit instantiation is the code above and nothing more) visits nothing new.  When closure ids
+// are asked for, the tie also lowers up[sub] to min(up[sub], S) — the smallest equal-count
+// superset one item larger — with an atomicMin issued only when the value read is larger.
+// k_closure_resolve then follows up[] from every node until kClosureNone (each step adds an item:
+// at most 63 steps) and writes the end point over up[v]: in a trie closed under subsets that is
+// the closed superset of equal support, whichever superset is taken at each step.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -85,12 +95,26 @@ __device__ __forceinline__ void mark(const C* __restrict__ count, unsigned char*
   if (count[sub] == c && eq[sub] != 1) eq[sub] = 1;
 }
 
-template <typename P, typename I, typename C>
+// the generator variant: S (node id s) marks its subset sub, and on a tie itself and up[sub]
+template <typename C>
+__device__ __forceinline__ void mark_gen(const C* __restrict__ count, unsigned char* sup,
+                                         unsigned char* eq, unsigned char* gen, unsigned int* up,
+                                         int32_t sub, int64_t s, C c) {
+  if (sup[sub] != 1) sup[sub] = 1;
+  if (count[sub] != c) return;
+  if (eq[sub] != 1) eq[sub] = 1;
+  if (gen[s] != 1) gen[s] = 1;
+  if (up != nullptr && __atomic_load_n(&up[sub], __ATOMIC_RELAXED) > (unsigned int)s)
+    atomicMin(&up[sub], (unsigned int)s);
+}
+
+template <bool kGen, typename P, typename I, typename C>
 __global__ __launch_bounds__(kBlock) void k_closed_mark(
     const P* __restrict__ parent, const I* __restrict__ item, const C* __restrict__ count,
     const unsigned char* __restrict__ depth, int64_t n,
     const unsigned long long* __restrict__ keys, const int32_t* __restrict__ vals,
-    unsigned long long mask, unsigned char* sup, unsigned char* eq, unsigned int* error) {
+    unsigned long long mask, unsigned char* sup, unsigned char* eq, unsigned int* error,
+    unsigned char* gen, unsigned int* up) {
   __shared__ int32_t s_path[kWaves][64];  // items of the run's parent P, root first
   __shared__ int32_t s_anc[kWaves][64];   // s_anc[i] = node of P's first i items (-1 for i = 0)
   __shared__ int32_t s_q[kWaves][64];     // s_q[j] = node of P minus its j-th item
@@ -149,9 +173,14 @@ __global__ __launch_bounds__(kBlock) void k_closed_mark(
         if (q < -1) continue;
         const int32_t sub = hlookup(keys, vals, mask, q, (int32_t)item[s]);
         if (sub < 0) atomicExch(error, 1u);
+        else if constexpr (kGen) mark_gen(count, sup, eq, gen, up, sub, s, count[s]);
         else mark(count, sup, eq, sub, count[s]);
       }
-      if (lane < r) mark(count, sup, eq, (int32_t)par, count[s0 + lane]);
+      if constexpr (kGen) {
+        if (lane < r) mark_gen(count, sup, eq, gen, up, (int32_t)par, s0 + lane, count[s0 + lane]);
+      } else {
+        if (lane < r) mark(count, sup, eq, (int32_t)par, count[s0 + lane]);
+      }
       wave_sync();  // the next run rewrites the LDS rows
       s0 += r;
     }
@@ -165,25 +194,73 @@ __global__ void k_closed_fold(unsigned char* __restrict__ sup, const unsigned ch
     sup[v] = (unsigned char)((eq[v] == 1 ? 0 : kFlagClosed) | (sup[v] == 1 ? 0 : kFlagMaximal));
 }
 
+// three-bit fold: bit 2 is the complement of the generator mark
+__global__ void k_closed_fold_gen(unsigned char* __restrict__ sup,
+                                  const unsigned char* __restrict__ eq,
+                                  const unsigned char* __restrict__ gen, int64_t n) {
+  const int64_t nthr = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += nthr)
+    sup[v] = (unsigned char)((eq[v] == 1 ? 0 : kFlagClosed) | (sup[v] == 1 ? 0 : kFlagMaximal) |
+                             (gen[v] == 1 ? 0 : kFlagGenerator));
+}
+
+// up[v] becomes the end of v's chain.  In place: every value a slot ever holds (the next step,
+// then the chain's end; the end's own slot holds itself) lies on its node's chain, so a walk that
+// reads a slot another thread has already resolved only skips ahead
+__global__ void k_closure_resolve(unsigned int* up, int64_t n) {
+  const int64_t nthr = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += nthr) {
+    unsigned int x = (unsigned int)v;
+    for (int step = 0; step < kMaxK; ++step) {
+      const unsigned int u = __atomic_load_n(&up[x], __ATOMIC_RELAXED);
+      if (u == kClosureNone || u == x || (int64_t)u >= n) break;
+      x = u;
+    }
+    __atomic_store_n(&up[v], x, __ATOMIC_RELAXED);
+  }
+}
+
 template <typename P, typename I, typename C>
 void run_marks(const P* parent, const I* item, const C* count, const unsigned char* depth,
                int64_t n, const ClosedScratch& x, int n_cus, hipStream_t s) {
   const int64_t n_chunks = (n + kChunk - 1) / kChunk;
   const int g = (int)std::min<int64_t>((int64_t)std::max(1, n_cus) * 8,
                                        (n_chunks + kWaves - 1) / kWaves);
-  hipLaunchKernelGGL((k_closed_mark<P, I, C>), dim3(g), dim3(kBlock), 0, s, parent, item, count,
-                     depth, n, (const unsigned long long*)x.keys, (const int32_t*)x.vals, x.mask,
-                     x.flags, x.eq, x.error);
-  KMLS_HIP(hipGetLastError());
   const int gf = (int)std::min<int64_t>(8192, (n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(k_closed_fold, dim3(gf), dim3(kBlock), 0, s, x.flags, x.eq, n);
+  if (x.gen == nullptr) {
+    if (x.up != nullptr) throw std::invalid_argument("closed flags: closure ids need the generator marks");
+    hipLaunchKernelGGL((k_closed_mark<false, P, I, C>), dim3(g), dim3(kBlock), 0, s, parent, item,
+                       count, depth, n, (const unsigned long long*)x.keys, (const int32_t*)x.vals,
+                       x.mask, x.flags, x.eq, x.error, (unsigned char*)nullptr,
+                       (unsigned int*)nullptr);
+    KMLS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_closed_fold, dim3(gf), dim3(kBlock), 0, s, x.flags, x.eq, n);
+    KMLS_HIP(hipGetLastError());
+    return;
+  }
+  hipLaunchKernelGGL((k_closed_mark<true, P, I, C>), dim3(g), dim3(kBlock), 0, s, parent, item,
+                     count, depth, n, (const unsigned long long*)x.keys, (const int32_t*)x.vals,
+                     x.mask, x.flags, x.eq, x.error, x.gen, x.up);
   KMLS_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_closed_fold_gen, dim3(gf), dim3(kBlock), 0, s, x.flags, x.eq,
+                     (const unsigned char*)x.gen, n);
+  KMLS_HIP(hipGetLastError());
+  if (x.up != nullptr) {
+    hipLaunchKernelGGL(k_closure_resolve, dim3(gf), dim3(kBlock), 0, s, x.up, n);
+    KMLS_HIP(hipGetLastError());
+  }
+}
+
+void clear_marks(const ClosedScratch& x, int64_t n, hipStream_t s) {
+  KMLS_HIP(hipMemsetAsync(x.flags, 0, (size_t)n, s));
+  KMLS_HIP(hipMemsetAsync(x.eq, 0, (size_t)n, s));
+  if (x.gen != nullptr) KMLS_HIP(hipMemsetAsync(x.gen, 0, (size_t)n, s));
+  if (x.up != nullptr) KMLS_HIP(hipMemsetAsync(x.up, 0xFF, (size_t)n * 4, s));  // kClosureNone
 }
 
 void clear(const ClosedScratch& x, int64_t n, hipStream_t s) {
   KMLS_HIP(hipMemsetAsync(x.keys, 0xFF, (size_t)(x.mask + 1) * 8, s));
-  KMLS_HIP(hipMemsetAsync(x.flags, 0, (size_t)n, s));
-  KMLS_HIP(hipMemsetAsync(x.eq, 0, (size_t)n, s));
+  clear_marks(x, n, s);
   KMLS_HIP(hipMemsetAsync(x.error, 0, 4, s));
 }
 
@@ -212,6 +289,14 @@ void closed_flags(const int64_t* parent, const int32_t* item, const uint32_t* co
   if (n <= 0) return;
   clear(x, n, s);
   rules_hash_build(parent, item, n, x.keys, x.vals, x.mask, s);
+  run_marks(parent, item, count, depth, n, x, n_cus, s);
+}
+
+void closed_marks(const int64_t* parent, const int32_t* item, const uint32_t* count,
+                  const unsigned char* depth, int64_t n, const ClosedScratch& x, int n_cus,
+                  hipStream_t s) {
+  if (n <= 0) return;
+  clear_marks(x, n, s);
   run_marks(parent, item, count, depth, n, x, n_cus, s);
 }
 

@@ -643,6 +643,10 @@ struct RuleArgs {
   int64_t* o_cons;
   double* o_conf;
   double* o_lift;
+  // min-max basis (basis != 0): only closed itemsets (set_flags bit 0) emit, and only antecedents
+  // that are generators (bit 2); set_flags = closed_marks(...) with a generator mark array
+  const unsigned char* set_flags = nullptr;
+  int basis = 0;
 };
 void rules_hash_build(const int64_t* parent, const int32_t* item, int64_t n,
                       unsigned long long* keys, int32_t* vals, unsigned long long mask,
@@ -653,9 +657,11 @@ void rules_pass(const RuleArgs& a, int grid, hipStream_t s);
 size_t rules_scan_temp_bytes(int64_t n);
 void rules_scan(const int64_t* in, int64_t* out, int64_t n, void* tmp, size_t tb, hipStream_t s);
 
-// ---- closed / maximal itemset flags (closed.hip) ----
-constexpr unsigned char kFlagClosed = 1;   // no proper superset in the trie has the same count
-constexpr unsigned char kFlagMaximal = 2;  // no proper superset in the trie
+// ---- closed / maximal / generator itemset flags and closure ids (closed.hip) ----
+constexpr unsigned char kFlagClosed = 1;     // no proper superset in the trie has the same count
+constexpr unsigned char kFlagMaximal = 2;    // no proper superset in the trie
+constexpr unsigned char kFlagGenerator = 4;  // no immediate subset in the trie has the same count
+constexpr unsigned int kClosureNone = 0xFFFFFFFFu;  // "no equal-count superset": never a node id
 struct ClosedScratch {        // device buffers of one call (cleared by it)
   unsigned long long* keys;   // [mask + 1] node hash (closed_hash_slots(n) slots)
   int32_t* vals;              // [mask + 1]
@@ -663,6 +669,10 @@ struct ClosedScratch {        // device buffers of one call (cleared by it)
   unsigned char* flags;       // [n] "has a superset" marks, then the result
   unsigned char* eq;          // [n] "has an equal-support superset" marks
   unsigned int* error;        // 0, 1 = a subset is missing from the trie, 2 = a path above 63
+  // asked for by being non-null: bit 2 of the result needs gen, closure ids need gen and up
+  unsigned char* gen = nullptr;  // [n] "has an equal-support immediate subset" marks
+  unsigned int* up = nullptr;    // [n] smallest equal-count one-item-larger superset (or
+                                 // kClosureNone), then, resolved in place, the closure id
 };
 uint64_t closed_hash_slots(int64_t n);  // power of two >= 2n (load factor <= 0.5)
 // one flag byte per node of a trie closed under subsets (n < 2^31 - 1), asynchronous on s: the
@@ -673,6 +683,11 @@ void closed_flags(const int64_t* parent, const int32_t* item, const uint32_t* co
 void closed_flags_narrow(const int32_t* parent, const void* item, bool item16,
                          const uint16_t* count, const unsigned char* depth, int64_t n,
                          const ClosedScratch& x, int n_cus, hipStream_t s);
+// closed_flags over a hash that the caller has already built in x.keys / x.vals (the rule engine's:
+// rules_hash_build): clears the mark arrays only; x.error is not cleared
+void closed_marks(const int64_t* parent, const int32_t* item, const uint32_t* count,
+                  const unsigned char* depth, int64_t n, const ClosedScratch& x, int n_cus,
+                  hipStream_t s);
 
 // ---- transaction builder (groupby.hip) ----
 // CSR of vals grouped by keys in [0, n_keys): rows sorted (and duplicate-free when dedup).

@@ -16,6 +16,12 @@
 //      (exact count ratio), lift, leverage, conviction; wave ballot compaction.
 // Pass 0 counts rules per itemset, an exclusive scan gives offsets, pass 1 writes — output
 // order (itemset, then mask) equals the CPU engine's, so results are bit-identical.
+//
+// Min-max basis (RuleArgs::basis): the rules g -> S \ g with S closed and g a generator; every
+// other rule has the supports and confidence of one of these.  set_flags holds closed.hip's
+// three-bit byte per node: an itemset that is not closed is skipped before its path chase and
+// subset table, and a mask is kept only if its antecedent node is a generator.  Same order, so
+// still the CPU engine's arrays.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -90,6 +96,12 @@ __global__ __launch_bounds__(kBlock) void k_rules(RuleArgs a) {
         if (a.pass == 0 && lane == 0) a.nrules[s] = 0;
         continue;
       }
+      // a skipped node leaves s_path and s_prev_parent as the last chased node left them, so the
+      // sibling shortcut below still sees the path that s_prev_parent names
+      if (a.basis && !(a.set_flags[s] & kFlagClosed)) {
+        if (a.pass == 0 && lane == 0) a.nrules[s] = 0;
+        continue;
+      }
       // 1. items of S (root → leaf order)
       const int64_t par = a.parent[s];
       if (lane == 0) {
@@ -147,6 +159,8 @@ __global__ __launch_bounds__(kBlock) void k_rules(RuleArgs a) {
           }
           if (na < 0 || nc < 0) {
             atomicExch(a.error, 1u);
+          } else if (a.basis && !(a.set_flags[na] & kFlagGenerator)) {
+            // not in the basis
           } else {
             const double cA = (double)a.count[na], cC = (double)a.count[nc];
             conf = (double)cS / cA;

@@ -28,6 +28,7 @@ __all__ = ["TransactionEncoder", "ItemsetTrie", "fpgrowth", "fpmax", "fpclose", 
 
 FLAG_CLOSED = 1   # no proper superset among the trie's itemsets has the same support
 FLAG_MAXIMAL = 2  # no proper superset among the trie's itemsets
+FLAG_GENERATOR = 4  # no immediate subset among the trie's itemsets has the same support
 # ItemsetTrie.flags(backend="auto") uploads the trie to the GPU from this many itemsets on.
 # Measured (profiles/closed_flags.md): at 18,624 itemsets the CPU twin still wins (1.0 ms against
 # 1.8 ms for itemset_flags_gpu, upload included); 77,905 is the first measured size where the GPU
@@ -85,11 +86,34 @@ class ItemsetTrie:
     stats: Dict = dataclasses.field(default_factory=dict)
     columns: Optional[Sequence] = None
     _flags: Optional[np.ndarray] = dataclasses.field(default=None, repr=False, compare=False)
+    _condensed: Optional[Dict] = dataclasses.field(default=None, repr=False, compare=False)
 
     def __len__(self) -> int:
         return int(len(self.item))
 
-    def flags(self, backend: str = "auto", device: int = 0) -> np.ndarray:
+    def _native_arrays(self):
+        return (np.ascontiguousarray(self.parent, np.int64),
+                np.ascontiguousarray(self.item, np.int32),
+                np.ascontiguousarray(self.count, np.uint32),
+                np.ascontiguousarray(self.depth, np.uint8))
+
+    def _condense(self, backend: str = "auto", device: int = 0) -> Dict:
+        """Three-bit flags and closure ids, computed once (cached apart from the two-bit bytes)."""
+        if self._condensed is None:
+            if backend == "auto":
+                backend = ("gpu" if (len(self) >= FLAGS_GPU_MIN_NODES and native.gpu_available())
+                           else "cpu")
+            if backend == "gpu":
+                r = native.require_gpu().itemset_condense_gpu(*self._native_arrays(), device)
+            elif backend == "cpu":
+                r = native.load().itemset_condense(*self._native_arrays())
+            else:
+                raise ValueError(f"unknown backend {backend!r}")
+            self._condensed = {"flags": r["flags"], "closure": r["closure"]}
+        return self._condensed
+
+    def flags(self, backend: str = "auto", device: int = 0, generators: bool = False
+              ) -> np.ndarray:
         """One byte per itemset: bit 0 (``FLAG_CLOSED``) no proper superset in this trie has the
         same support, bit 1 (``FLAG_MAXIMAL``) no proper superset is in this trie.  Computed once
         and cached.  The flags are relative to the trie: mined with ``max_len``, an itemset of
@@ -97,7 +121,13 @@ class ItemsetTrie:
 
         ``backend``: "gpu" (HIP kernel, csrc/kernels/closed.hip), "cpu" (threaded C++ twin, same
         bytes), "auto" (GPU when one is visible and the trie is large enough to pay for the
-        upload).  Raises if a subset of an itemset is missing from the trie."""
+        upload).  Raises if a subset of an itemset is missing from the trie.
+
+        ``generators=True``: the bytes also carry bit 2 (``FLAG_GENERATOR``): no immediate subset
+        in this trie has the same support (singletons always are generators; the bit looks only at
+        subsets, so ``max_len`` does not change it).  Cached separately."""
+        if generators:
+            return self._condense(backend, device)["flags"]
         if self._flags is None:
             args = (np.ascontiguousarray(self.parent, np.int64),
                     np.ascontiguousarray(self.item, np.int32),
@@ -121,6 +151,17 @@ class ItemsetTrie:
     def maximal_mask(self, backend: str = "auto") -> np.ndarray:
         """Boolean mask of the maximal itemsets (see :meth:`flags`)."""
         return (self.flags(backend) & FLAG_MAXIMAL) != 0
+
+    def generator_mask(self, backend: str = "auto") -> np.ndarray:
+        """Boolean mask of the generators (free / key itemsets; see :meth:`flags`)."""
+        return (self.flags(backend, generators=True) & FLAG_GENERATOR) != 0
+
+    def closure(self, backend: str = "auto") -> np.ndarray:
+        """Node id of every itemset's closure: from the itemset, step to the smallest-id superset
+        one item larger with the same support until there is none.  In a trie mined without
+        ``max_len`` that is the unique closed superset of equal support; with ``max_len`` it is a
+        closure relative to the trie.  ``closure()[v] == v`` exactly when ``v`` is closed."""
+        return self._condense(backend)["closure"]
 
     @property
     def support(self) -> np.ndarray:

@@ -23,6 +23,7 @@ from ..ops import native
 from .fpgrowth import ItemsetTrie, csr_from_lists, mine_csr
 
 _METRICS = {"confidence": 0, "lift": 1, "leverage": 2, "support": 3, "conviction": 4}
+_BASES = {"all": 0, "minmax": 1}
 
 
 class Rules:
@@ -85,12 +86,20 @@ class Rules:
 
 def rules_from_trie(trie: ItemsetTrie, metric: str = "confidence", min_threshold: float = 0.8,
                     max_antecedent: int = 0, strict: bool = False, backend: str = "auto",
-                    device: int = 0) -> Rules:
+                    device: int = 0, basis: str = "all") -> Rules:
     """``backend``: "gpu" (HIP rule_score kernels, csrc/kernels/rules.hip), "cpu" (threaded
     C++), "auto" (GPU when one is visible and the trie is large enough to amortise the upload).
-    Both produce identical rules in identical order."""
+    Both produce identical rules in identical order.
+
+    ``basis``: "all" (every antecedent of every itemset) or "minmax" — the min-max basis: only
+    rules ``g -> c \\ g`` with ``c`` a closed itemset and ``g`` a generator (see
+    :meth:`ItemsetTrie.flags`).  Any rule ``A -> C`` has the supports and confidence of the basis
+    rule with itemset ``closure(A ∪ C)`` and an antecedent whose closure is ``closure(A)``; the
+    exact rules are those with ``confidence == 1.0``.  The other filters apply unchanged."""
     if metric not in _METRICS:
         raise ValueError(f"unknown metric {metric!r}; choose from {sorted(_METRICS)}")
+    if basis not in _BASES:
+        raise ValueError(f"unknown basis {basis!r}; choose from {sorted(_BASES)}")
     m = 5 if (strict and metric == "confidence") else _METRICS[metric]
     args = (np.ascontiguousarray(trie.parent, np.int64), np.ascontiguousarray(trie.item, np.int32),
             np.ascontiguousarray(trie.count, np.uint32), np.ascontiguousarray(trie.depth, np.uint8),
@@ -98,9 +107,9 @@ def rules_from_trie(trie: ItemsetTrie, metric: str = "confidence", min_threshold
     if backend == "auto":
         backend = "gpu" if (len(trie) >= 50_000 and native.gpu_available()) else "cpu"
     if backend == "gpu":
-        raw = native.require_gpu().association_rules_gpu(*args, device)
+        raw = native.require_gpu().association_rules_gpu(*args, device, _BASES[basis])
     elif backend == "cpu":
-        raw = native.load().association_rules(*args)
+        raw = native.load().association_rules(*args, 0, _BASES[basis])
     else:
         raise ValueError(f"unknown backend {backend!r}")
     return Rules(trie, raw)
@@ -108,13 +117,13 @@ def rules_from_trie(trie: ItemsetTrie, metric: str = "confidence", min_threshold
 
 def association_rules(frequent, num_itemsets: Optional[int] = None, metric: str = "confidence",
                       min_threshold: float = 0.8, support_only: bool = False,
-                      use_colnames: bool = True):
+                      use_colnames: bool = True, basis: str = "all"):
     """mlxtend-compatible entry point.  ``frequent`` is an :class:`ItemsetTrie` (as returned by
     ``fpgrowth(..., as_trie=True)``) — the DataFrame form is accepted too (re-indexed)."""
     trie = frequent if isinstance(frequent, ItemsetTrie) else _trie_from_df(frequent, num_itemsets)
     if support_only:
         metric, min_threshold = "support", 0.0
-    return rules_from_trie(trie, metric, min_threshold).to_dataframe(use_colnames)
+    return rules_from_trie(trie, metric, min_threshold, basis=basis).to_dataframe(use_colnames)
 
 
 def _trie_from_df(df, num_itemsets: Optional[int]) -> ItemsetTrie:

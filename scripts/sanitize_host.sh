@@ -13,6 +13,6 @@ case "$mode" in
 esac
 out=build/sanitize-$mode
 mkdir -p "$out"
-src="csrc/host/csv_encode.cpp csrc/host/miner_cpu.cpp csrc/host/matcher_cpu.cpp csrc/host/rules_cpu.cpp csrc/host/synth.cpp csrc/tests/host_selftest.cpp"
+src="csrc/host/csv_encode.cpp csrc/host/miner_cpu.cpp csrc/host/matcher_cpu.cpp csrc/host/rules_cpu.cpp csrc/host/closed_cpu.cpp csrc/host/synth.cpp csrc/tests/host_selftest.cpp"
 g++ -std=c++17 -O1 -g -fno-omit-frame-pointer $flags -Icsrc/include $src -o "$out/host_selftest" -pthread
 "$out/host_selftest"
