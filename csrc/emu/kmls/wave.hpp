@@ -9,6 +9,7 @@ namespace kmls {
 namespace kern {
 
 inline unsigned vzero() { return 0u; }
+inline void keep64(unsigned long long&) {}
 
 template <typename T>
 using gptr = T*;

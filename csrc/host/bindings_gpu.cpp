@@ -529,6 +529,9 @@ void register_gpu_bindings(py::module_& m) {
         d["spilled_tasks"] = r.spilled_tasks;
         d["handoffs"] = r.handoffs;
         d["leaf_candidates"] = r.leaf_candidates;
+        d["leaf_steps"] = r.leaf_steps;
+        d["batch_steps"] = r.batch_steps;
+        d["row_steps"] = r.row_steps;
         d["leaf_m_default"] = gpu::kDeepLeafDefault;
         d["leaf_m_max"] = kern::deep_leaf_max();
         d["round_ms"] = r.round_ms;

@@ -115,6 +115,9 @@ DeepResult GpuMiner::mine_deep(double min_support, int max_len, int rank, int wo
   res.spilled_tasks = loc.spilled_tasks;
   res.handoffs = loc.handoffs;
   res.leaf_candidates = (int64_t)loc.leaf_candidates;
+  res.leaf_steps = (int64_t)loc.leaf_steps;
+  res.batch_steps = (int64_t)loc.batch_steps;
+  res.row_steps = (int64_t)loc.row_steps;
   res.round_ms = loc.round_ms;
   res.ms_root = loc.ms_root;
   res.ms_rounds = loc.ms_rounds;

@@ -587,6 +587,9 @@ DeepLocal deep_run(DeepBufs& b, const DeepInput& in, int rank, int world, const 
   res.dxor = b.h_ctl->digest_xor;
   res.candidates = b.h_ctl->candidates;
   res.leaf_candidates = b.h_ctl->leaf_candidates;
+  res.leaf_steps = b.h_ctl->leaf_steps;
+  res.batch_steps = b.h_ctl->batch_steps;
+  res.row_steps = b.h_ctl->row_steps;
   res.chunks = b.h_ctl->chunks;
   return res;
 }

@@ -108,6 +108,7 @@ struct DeepLocal {
   std::vector<uint64_t> per_depth = std::vector<uint64_t>(64, 0);
   uint64_t dsum = 0, dxor = 0, candidates = 0, chunks = 0;
   uint64_t leaf_candidates = 0;  // of candidates: subsets evaluated by leaf steps
+  uint64_t leaf_steps = 0, batch_steps = 0, row_steps = 0;  // the count kernel's steps, by kind
   int64_t level2_tasks = 0;
   int maxt = 0;  // widest block tier of the count kernel instance
   std::vector<int64_t> round_tasks;

@@ -201,6 +201,7 @@ struct DeepResult {
   // every subset of a small class, so the total may exceed the depth-first walk's.  Of them,
   // leaf_candidates were evaluated in leaf steps (this rank's; 0 = the path did not run).
   int64_t leaf_candidates = 0;
+  int64_t leaf_steps = 0, batch_steps = 0, row_steps = 0;  // the count kernel's steps, by kind
   std::vector<double> round_ms;
   double ms_prologue = 0, ms_root = 0, ms_rounds = 0, ms_combine = 0, ms_total = 0;
   double ms_assign = 0;               // task costs + ordering (inside ms_root)

@@ -20,6 +20,11 @@ __device__ __forceinline__ unsigned vzero() {
   return z;
 }
 
+// Pins a loaded value at this point of the program: the load that produces it is issued (and
+// waited for) before here, so the compiler cannot sink it into a later branch, where it would be
+// a dependent round trip of its own after the loads it was meant to fly with.
+__device__ __forceinline__ void keep64(unsigned long long& v) { asm volatile("" : "+v"(v)); }
+
 // A pointer the compiler must treat as GLOBAL memory (address space 1).  A row pointer rebuilt
 // from an integer (a frame's block address) is otherwise generic, so its loads become flat_load:
 // those count in lgkmcnt as well as vmcnt and may return out of order, so every later wait for

@@ -291,6 +291,9 @@ __device__ __forceinline__ void write_proj(unsigned long long* cb, unsigned long
   if (surv) cb[(unsigned long long)wt_out * cpad + pos] = ih;
 }
 
+// the kinds of step
+enum StepKind { kStepBatch = 0, kStepRow = 1, kStepLeaf = 2 };
+
 template <int MAXT>
 struct WaveLds {
   unsigned long long f_hash[kBatchFrames];
@@ -314,6 +317,7 @@ struct WaveLds {
   unsigned b_live[kBStack];
   unsigned long long depth_cnt[64];
   unsigned long long leaf_cands;    // subsets evaluated by leaf steps (of WaveAcc::cands)
+  unsigned n_steps[4];              // steps taken, by StepKind
   ProjLds<MAXT> proj;
 };
 
@@ -632,8 +636,10 @@ __device__ __forceinline__ void row_step(const DeepArgs& a, DeepFrame* fst, Wave
     unsigned long long v[WT];
     // the candidate's item hash is loaded with its row words (96 % of the candidates survive
     // at the headline): one round trip per chunk instead of a second one after the count
-    const unsigned long long ih_ld = ihp[jb];
+    // (pinned ahead of the survivor branch, or the compiler sinks the load into it)
+    unsigned long long ih_ld = ihp[jb];
     const unsigned c = and_count<WT>(blk, top.pad, ia + vzero(), jb, v);
+    keep64(ih_ld);
     const bool surv = act && c >= a.minsup;
     const unsigned long long mask = __ballot(surv);
     const unsigned pos = S + (unsigned)__popcll(mask & lanelt);
@@ -661,8 +667,8 @@ __device__ __forceinline__ void row_step(const DeepArgs& a, DeepFrame* fst, Wave
       }
     }
     S += (unsigned)__popcll(mask);
-    ++acc.chunks;
   }
+  acc.chunks += (nc + 63) / 64;
   acc.cands += nc;
   if (lane == 0 && S) L.depth_cnt[depth + 2] += S;
   acc.budget_used += (nc + 63) / 64;
@@ -792,8 +798,10 @@ __device__ __forceinline__ void batch_step(const DeepArgs& a, DeepFrame* fst, Wa
     const unsigned sa = L.f_s0[f] + i, sb = L.f_s0[f] + (act ? j : i);
     unsigned long long v[WT];
     // item hashes in flight with the row words (see row_step)
-    const unsigned long long ih_la = ihp[sa], ih_lb = ihp[sb];
+    unsigned long long ih_la = ihp[sa], ih_lb = ihp[sb];
     const unsigned c = and_count<WT>(bblk, bpad, sa, sb, v);
+    keep64(ih_la);
+    keep64(ih_lb);
     const bool surv = act && c >= a.minsup;
     const unsigned long long mask = __ballot(surv);
     // member groups are runs of consecutive lanes: the first lane of each run updates its
@@ -833,11 +841,11 @@ __device__ __forceinline__ void batch_step(const DeepArgs& a, DeepFrame* fst, Wa
         }
       }
     }
-    // the batch's frames are siblings of one block: one depth
-    if (lane == 0 && mask) L.depth_cnt[meta_depth(top.meta) + 2] += (unsigned long long)__popcll(mask);
     S += (unsigned)__popcll(mask);
-    ++acc.chunks;
   }
+  acc.chunks += (P + 63) / 64;
+  // the batch's frames are siblings of one block: one depth, counted once per step
+  if (lane == 0 && S) L.depth_cnt[meta_depth(top.meta) + 2] += S;
   acc.cands += P;
   acc.budget_used += (P + 63) / 64;
   // the k consumed frames leave the stack
@@ -900,12 +908,23 @@ __device__ __forceinline__ void batch_step(const DeepArgs& a, DeepFrame* fst, Wa
 // The frames' member rows are staged in LDS once per step: frames of one block lie next to each
 // other in slot order (their singleton neighbours between them), so the step stages the slot
 // range the run spans and ends the run where that range outgrows the stage.
+// A pass reads one staged row per member of the lane's subset.  At the narrow tiers the reads of
+// leaf_flat<WT>() members are issued together and waited for once, without a branch per member: a
+// member the subset leaves out reads a neutral slot instead (all-ones words, item hash 0; the
+// first kLeafMax slots of every staged row).  At the wider tiers, where that many rows in flight
+// do not fit the registers, each member of the subset is a branch with its own reads.
+template <int WT>
+constexpr unsigned leaf_flat() { return WT <= 2 ? 4u : WT <= 4 ? 2u : 0u; }
+
 template <int WT, int MAXT>
 __device__ __forceinline__ void leaf_step(const DeepArgs& a, WaveState& st, WaveLds<MAXT>& L,
                                           const DeepFrame& top, const DeepFrame& lf, int lane,
                                           WaveAcc& acc) {
   static_assert(WT <= kLeafTier, "leaf step tiers");
   constexpr unsigned kStride = (unsigned)kLeafStage / (unsigned)(WT + 1);  // slots per staged row
+  constexpr unsigned kFlat = leaf_flat<WT>();
+  constexpr unsigned kLead = kFlat ? (unsigned)kLeafMax : 0u;  // neutral slots ahead of the range
+  static_assert(kFlat == 0 || kLeafMax % kFlat == 0, "member groups");
   const unsigned depth = meta_depth(top.meta);
   // frame f (from the top) = lane f's registers, as in batch_step
   const unsigned fm = lf.m;
@@ -944,7 +963,7 @@ __device__ __forceinline__ void leaf_step(const DeepArgs& a, WaveState& st, Wave
   if ((unsigned)lane < k) {
     const unsigned base = incl - fc;
     L.f_hash[lane] = lf.hash;
-    L.f_s0[lane] = lf.s0 - smin;
+    L.f_s0[lane] = lf.s0 - smin + kLead;
     L.f_meta[lane] = lf.meta;
     L.P[lane] = base;
     atomicOr(&L.g_flag[base >> 6], 1ull << (base & 63));  // (every frame has >= 1 subset)
@@ -954,33 +973,69 @@ __device__ __forceinline__ void leaf_step(const DeepArgs& a, WaveState& st, Wave
 #pragma unroll
     for (int w = 0; w <= WT; ++w) {
       const gptr<const unsigned long long> row = blk + (unsigned long long)w * top.pad + smin;
-      for (unsigned j = lane; j < range; j += 64) L.leaf_rows[(unsigned)w * kStride + j] = row[j];
+      for (unsigned j = lane; j < range; j += 64)
+        L.leaf_rows[(unsigned)w * kStride + kLead + j] = row[j];
+      // (the neutral slots take the place of the kLeafMax slots of slack behind the range)
+      if (kFlat && lane < kLeafMax) L.leaf_rows[(unsigned)w * kStride + lane] = w < WT ? ~0ull : 0ull;
     }
   }
   __builtin_amdgcn_wave_barrier();
-  unsigned fbase = 0, dc = 0;  // dc: lane kk's count of frequent subsets of kk members
-  unsigned long long evaluated = 0;
+  // Lanes of one pass differ in size, so each lane tallies its own frequent subsets by size: the
+  // 8-bit field kk - 2 of `tally` counts those of kk members (a lane sees <= kLeafSlots / 64
+  // passes per step), summed over the lanes once per step, after the passes.
+  static_assert(kLeafSlots / 64 * 16 <= 255 && kLeafMax - 2 < 8, "tally fields");
+  const bool capped = a.max_len != 0;
+  // the largest subset still counted (the cap is on the itemset's size, prefix included)
+  const unsigned kk_cap = !capped ? 64u : a.max_len > (int)depth ? (unsigned)a.max_len - depth : 0u;
+  unsigned fbase = 0, ev = 0;  // ev: this lane's evaluated subsets
+  unsigned long long tally = 0;
   for (unsigned c0 = 0; c0 < total; c0 += 64) {
     const unsigned p = c0 + lane;
     const unsigned long long gw = uni64(L.g_flag[(c0 >> 6) + vzero()]);
     // the lane's frame: frame starts at or before its slot (lanes past the end: the last frame)
     const unsigned f = fbase + (unsigned)__popcll(gw & ((2ull << lane) - 1ull)) - 1u;
     fbase += (unsigned)__popcll(gw);
-    const unsigned mask = p < total ? leaf_subset(p - L.P[f]) : 3u;
+    // (lanes past the end redo the last subset, so the three table reads need no branch and
+    // share one wait)
+    const unsigned mask = leaf_subset((p < total ? p : total - 1u) - L.P[f]);
     const unsigned kk = (unsigned)__popc(mask);
-    const bool act = p < total && (a.max_len == 0 || (int)(depth + kk) <= a.max_len);
+    const bool act = p < total && kk <= kk_cap;
     const unsigned o = L.f_s0[f];
     unsigned long long h = L.f_hash[f];
     unsigned long long v[WT];
 #pragma unroll
     for (int w = 0; w < WT; ++w) v[w] = ~0ull;
-#pragma unroll kLeafUnroll
-    for (unsigned i = 0; i < (unsigned)kLeafMax; ++i) {
-      if (i >= mmax) break;  // (uniform)
-      if ((mask >> i) & 1u) {
+    if constexpr (kFlat != 0) {
+      const unsigned o8 = o * 8u;  // byte offset of the frame's first member in a staged row
 #pragma unroll
-        for (int w = 0; w < WT; ++w) v[w] &= L.leaf_rows[(unsigned)w * kStride + o + i];
-        h += L.leaf_rows[(unsigned)WT * kStride + o + i];
+      for (unsigned i0 = 0; i0 < (unsigned)kLeafMax; i0 += kFlat) {
+        if (i0 && i0 >= mmax) break;  // (uniform)
+        unsigned long long r[kFlat][WT + 1];
+#pragma unroll
+        for (unsigned j = 0; j < kFlat; ++j) {
+          // member i0 + j's slot if the subset has it, else neutral slot i0 + j
+          const unsigned sel = (0u - ((mask >> (i0 + j)) & 1u)) & o8;
+          const unsigned long long* mp =
+              (const unsigned long long*)((const char*)&L.leaf_rows[i0 + j] + sel);
+#pragma unroll
+          for (int w = 0; w <= WT; ++w) r[j][w] = mp[(unsigned)w * kStride];
+        }
+#pragma unroll
+        for (unsigned j = 0; j < kFlat; ++j) {
+#pragma unroll
+          for (int w = 0; w < WT; ++w) v[w] &= r[j][w];
+          h += r[j][WT];
+        }
+      }
+    } else {
+#pragma unroll kLeafUnroll
+      for (unsigned i = 0; i < (unsigned)kLeafMax; ++i) {
+        if (i >= mmax) break;  // (uniform)
+        if ((mask >> i) & 1u) {
+#pragma unroll
+          for (int w = 0; w < WT; ++w) v[w] &= L.leaf_rows[(unsigned)w * kStride + o + i];
+          h += L.leaf_rows[(unsigned)WT * kStride + o + i];
+        }
       }
     }
     unsigned c = 0;
@@ -991,19 +1046,31 @@ __device__ __forceinline__ void leaf_step(const DeepArgs& a, WaveState& st, Wave
       const DigestTerms dt = digest_terms(h, c);
       acc.dsum += dt.sum;
       acc.dxor ^= dt.xr;
+      tally += 1ull << ((kk - 2u) * 8u);
     }
-    // lanes of one pass differ in size: one ballot per size, counted by lane kk
-#pragma unroll
-    for (unsigned q = 2; q <= (unsigned)kLeafMax; ++q) {
-      if (q > mmax) break;  // (uniform)
-      const unsigned n = (unsigned)__popcll(__ballot(surv && kk == q));
-      if ((unsigned)lane == q) dc += n;
-    }
-    evaluated += (unsigned long long)__popcll(__ballot(act));
-    ++acc.chunks;
+    ev += act ? 1u : 0u;
   }
-  if ((unsigned)lane >= 2u && (unsigned)lane <= mmax && dc && depth + (unsigned)lane < 64u)
-    L.depth_cnt[depth + (unsigned)lane] += dc;
+  acc.chunks += (total + 63) / 64;
+  // 16 lanes' fields still fit 8 bits (16 x 8 passes); then the even and the odd fields apart,
+  // 16 bits each, over the four groups of 16 lanes
+  for (int off = 1; off < 16; off <<= 1) tally += shfl_xor64(tally, off);
+  unsigned long long t_even = tally & 0x00ff00ff00ff00ffull;        // kk = 2, 4, 6, 8
+  unsigned long long t_odd = (tally >> 8) & 0x00ff00ff00ff00ffull;  // kk = 3, 5, 7
+  for (int off = 16; off < 64; off <<= 1) {
+    t_even += shfl_xor64(t_even, off);
+    t_odd += shfl_xor64(t_odd, off);
+  }
+  if ((unsigned)lane >= 2u && (unsigned)lane <= (unsigned)kLeafMax) {  // lane kk: size kk's count
+    const unsigned q = (unsigned)lane - 2u;
+    const unsigned n = (unsigned)(((q & 1u) ? t_odd : t_even) >> ((q >> 1) * 16u)) & 0xffffu;
+    if (n && depth + (unsigned)lane < 64u) L.depth_cnt[depth + (unsigned)lane] += n;
+  }
+  // every subset is evaluated unless a size cap leaves the larger ones out
+  unsigned long long evaluated = total;
+  if (capped) {
+    for (int off = 32; off; off >>= 1) ev += __shfl_xor(ev, off, 64);
+    evaluated = uni(ev);
+  }
   acc.cands += evaluated;
   if (lane == 0) L.leaf_cands += evaluated;
   acc.budget_used += (total + 63) / 64;
@@ -1015,9 +1082,6 @@ __device__ __forceinline__ void leaf_step(const DeepArgs& a, WaveState& st, Wave
   st.nf -= k;
   __builtin_amdgcn_wave_barrier();
 }
-
-// the kinds of step
-enum StepKind { kStepBatch = 0, kStepRow = 1, kStepLeaf = 2 };
 
 // one step of the top frame, dispatched on its block width (wave-uniform)
 template <int MAXT, bool EMIT, int T0, int... Ts>
@@ -1065,6 +1129,7 @@ __global__ __launch_bounds__(256, WPS) __attribute__((amdgpu_waves_per_eu(WPS)))
 
   for (int d = lane; d < 64; d += 64) L.depth_cnt[d] = 0;
   if (lane == 0) L.leaf_cands = 0;
+  if (lane < 4) L.n_steps[lane] = 0;
   WaveAcc acc{0, 0, 0, 0, 0};
   __builtin_amdgcn_wave_barrier();
 
@@ -1279,9 +1344,10 @@ __global__ __launch_bounds__(256, WPS) __attribute__((amdgpu_waves_per_eu(WPS)))
         failed = true;
         break;
       }
-      step_tier<MAXT, EMIT, 1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64>(
-          wt, leaf_mode ? kStepLeaf : row_mode ? kStepRow : kStepBatch, a, fst, st, L, top, lf, stack,
-          lane, acc);
+      const StepKind kind = leaf_mode ? kStepLeaf : row_mode ? kStepRow : kStepBatch;
+      if (lane == 0) atomicAdd(&L.n_steps[kind], 1u);  // (an LDS add without a return: no wait)
+      step_tier<MAXT, EMIT, 1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64>(wt, kind, a, fst, st, L, top, lf,
+                                                                      stack, lane, acc);
       free_blocks(L, st);
     }
     if (tr && !failed && lane == 0) {
@@ -1334,6 +1400,9 @@ __global__ __launch_bounds__(256, WPS) __attribute__((amdgpu_waves_per_eu(WPS)))
     atomicAdd(&a.ctl->candidates, acc.cands);
     atomicAdd(&a.ctl->chunks, acc.chunks);
     if (L.leaf_cands) atomicAdd(&a.ctl->leaf_candidates, L.leaf_cands);
+    if (L.n_steps[kStepLeaf]) atomicAdd(&a.ctl->leaf_steps, (unsigned long long)L.n_steps[kStepLeaf]);
+    if (L.n_steps[kStepBatch]) atomicAdd(&a.ctl->batch_steps, (unsigned long long)L.n_steps[kStepBatch]);
+    if (L.n_steps[kStepRow]) atomicAdd(&a.ctl->row_steps, (unsigned long long)L.n_steps[kStepRow]);
   }
   for (int d = lane; d < 64; d += 64)
     if (L.depth_cnt[d]) atomicAdd(&a.ctl->per_depth[d], L.depth_cnt[d]);

@@ -40,6 +40,7 @@ struct DeepCtl {  // per-round control + accumulated results (zeroed once per ca
   unsigned pad_[3];
   unsigned long long t_drain;     // (trace) wall clock when the last queued task was dequeued
   unsigned long long leaf_candidates;  // subsets evaluated by leaf steps (part of `candidates`)
+  unsigned long long leaf_steps, batch_steps, row_steps;  // steps the waves took, by kind
 };
 struct DeepArgs {
   const DeepFrame* in;
